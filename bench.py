@@ -8,14 +8,19 @@ network the reference's dual_network() writes as best.pth), then the move is
 sampled and recorded on device. Finished games are replaced by new ones, so
 every step keeps `games` trees in flight.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU; games sharded by global id in
                                                        contiguous blocks, no collective on the data path)
 
-Rank 0 prints ONE JSON line: the headline (BASELINE.json's 4096 x 50 config), the
+Rank 0 prints ONE JSON line. A plain run does only what the headline needs (BASELINE.json's
+4096 x 50 config): set up, age and warm up the population, time the K steps, print metric, value,
+unit, ms_per_step, dtype and the configuration. --dump-outputs DIR then writes the records of the
+games that ended in the last timed step (what SelfPlay.records() hands a caller) as DIR/<name>.npy.
+
+--full adds everything else, each from runs of its own after the timed steps: the
 roofline of the dominant kernel (the residual-tower conv, MFMA), the north star's
-select and backup kernels against HBM, and - at N=1 - extra configurations
-(`variants`: non-saturated network, evaluation cache off, C3 4096 x 400) and
+select and backup kernels against HBM (a separate instrumented pass), and - at N=1 -
+extra configurations (`variants`: non-saturated network, evaluation cache off, C3 4096 x 400) and
 the CPU baselines (`cpu_baseline`: the reference's own C++ search with its
 DualNetwork on the host cores; `cpu_baselines`: BASELINE.md's B-tree and B-e2e).
 """
@@ -77,11 +82,17 @@ def parse():
     ap.add_argument("--cache-log2", type=int, default=23, help="evaluation cache entries (log2); 0 = off")
     ap.add_argument("--cache-clear-every", type=int, default=0,
                     help="moves between evaluation-cache clears (0: never; full probe windows replace entries)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the records of the games that ended in the last timed step "
+                         "(policies, actions, values, states, game ids, lengths) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the instrumented pass (rooflines, breakdowns), "
+                         "the variants, the isolated conv timing and the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the variants")
     ap.add_argument("--no-isolated", action="store_true",
-                    help="skip the isolated conv timing after the timed region (rocprof window runs)")
+                    help="with --full: skip the isolated conv timing after the timed region (rocprof window runs)")
     # rehearsal of the multi-rank path on a one-GPU box: every rank on device 0, gloo instead of RCCL
     ap.add_argument("--rehearse-shared-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-child", choices=["cpu-nn", "tree", "device-nn"], help=argparse.SUPPRESS)
@@ -210,9 +221,79 @@ def union_ms(intervals):
     return busy + (cur[1] - cur[0] if cur is not None else 0.0)
 
 
+DUMP_MAX_PLIES = 80_000  # x 720 B per ply (81 f64 policy, 8 f64 state words, action, value) = 57.6 MB < 64 MB
+
+
+def watch_finished(sp):
+    """Per lane, the list that every later move end appends its finished-game count to (the engine's
+    move_result / move_end, whichever the step loop calls): the count before a call's last move tells which
+    games that move ended. A Python append per move, no device work."""
+    logs = []
+    for ln in sp.lanes:
+        log = []
+        for name, pick in (("move_result", lambda r: r[0]), ("move_end", lambda r: r)):
+            def call(orig=getattr(ln.engine, name), pick=pick, log=log):
+                r = orig()
+                log.append(pick(r))
+                return r
+            setattr(ln.engine, name, call)
+        logs.append(log)
+    return logs
+
+
+def last_step_outputs(sp, logs, start):
+    """The records of the games whose last move was the final timed step, as SelfPlay.records() returns them
+    (policy targets f64, actions, values, packed states), concatenated in game-id order. A lane's arena grows in
+    finishing order, so the last move's games are the lane's newest arena rows. More than DUMP_MAX_PLIES plies:
+    a fixed seeded sample of the games."""
+    import numpy as np
+    picked = []
+    for ln, log, s0 in zip(sp.lanes, logs, start):
+        ids, off, lens = ln.engine.games()
+        before = log[-2] if len(log) >= 2 else s0
+        new = np.argsort(off, kind="stable")[min(before, len(ids)):]
+        if not len(new):
+            continue
+        pl = ln.engine.plies(with_inputs=False)
+        for j in new:
+            o, n = int(off[j]), int(lens[j])
+            picked.append((int(ids[j]), {k: pl[k][o:o + n] for k in ("policies", "actions", "values", "states")}))
+    picked.sort(key=lambda t: t[0])
+    ended = len(picked)
+    if sum(len(r["actions"]) for _, r in picked) > DUMP_MAX_PLIES:
+        keep, plies = [], 0
+        for j in np.random.RandomState(0).permutation(len(picked)):
+            n = len(picked[j][1]["actions"])
+            if plies + n <= DUMP_MAX_PLIES:
+                keep.append(j)
+                plies += n
+        picked = [picked[j] for j in sorted(keep)]
+    recs = [r for _, r in picked]
+
+    def cat(key, dtype, tail=()):
+        return np.concatenate([r[key].astype(dtype) for r in recs]) if recs else np.zeros((0,) + tail, dtype)
+
+    st = np.concatenate([r["states"] for r in recs]) if recs else None
+    states = (np.concatenate([st["own"], st["opp"], st["mains"][:, None], st["active"][:, None]],
+                             axis=1).astype(np.float64) if recs else np.zeros((0, 8), np.float64))
+    return {"game_ids": np.array([g for g, _ in picked], np.float64),
+            "game_lengths": np.array([len(r["actions"]) for r in recs], np.float64),
+            "policies": cat("policies", np.float64, (81,)), "actions": cat("actions", np.float32),
+            "values": cat("values", np.float32), "states": states,
+            "counts": np.array([ended, len(recs), sp.finished], np.float64)}
+
+
+def write_outputs(path, outputs, rank, world):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def run_config(net, local, rank, world, games, sims, batch, lanes, cache_log2, age, warmup, steps, evaluator,
-               cache_clear_every=0, instrument=True):
-    """Continuous self-play of `games` slots on this GPU; returns the timed-window statistics."""
+               cache_clear_every=0, instrument=True, dump=False):
+    """Continuous self-play of `games` slots on this GPU; returns the timed-window statistics (dump: and
+    the last timed step's records, "outputs")."""
     import torch
     import torch.distributed as dist
     from uttt_amd import HashEvaluator, NetworkEvaluator, SelfPlay
@@ -283,6 +364,8 @@ def run_config(net, local, rank, world, games, sims, batch, lanes, cache_log2, a
     # the kernel rooflines then have no times)
     sp.set_timing(instrument)
     rounds0, finished0, leaves0 = sp.rounds, sp.finished, sp.leaves
+    lane_finished0 = [ln.finished for ln in sp.lanes]
+    finished_logs = watch_finished(sp) if dump else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -309,6 +392,10 @@ def run_config(net, local, rank, world, games, sims, batch, lanes, cache_log2, a
            "rounds": sp.rounds - rounds0, "finished": sp.finished - finished0,
            "conv": "wino3h_f16" if evaluator == "fused_f16" else conv,
            "cache": sp.cache_stats() if cache_log2 else None, "trees_per_launch": games // lanes}
+    if dump:
+        out["outputs"] = last_step_outputs(sp, finished_logs, lane_finished0)
+        for ln in sp.lanes:  # the wrappers hold their engine: without them `del sp` frees it at once
+            del ln.engine.move_result, ln.engine.move_end
     del sp
     torch.cuda.empty_cache()
     return out
@@ -593,6 +680,50 @@ def tree_rooflines(stats, trees, evaluator, sims, pmc_sel, pmc_app):
                                       "UTTT_FUSED_ROUNDS=0 measures k_apply on its own"}
 
 
+def headline(args, world, value, max_elapsed):
+    """The result line of a plain run (the first fields of a --full run's): the measurement and its configuration."""
+    G, S, B = args.games, args.sims, args.batch
+    return {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "simulations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(max_elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"fused": "f32 activations and accumulation; tower point GEMMs as 3-term split-f16 products "
+                           "on the f16 MFMA (f32-level accuracy: within 1e-5 of the reference's fp32 network)",
+                  "fused_f16": "f32 activations and accumulation; tower point GEMMs as ONE f16 product (the "
+                               "optional f16 mode: ~1e-2 on the network's outputs, not the reference's numerics)",
+                  "nn": "f32", "hash": "f32 (hash evaluator)"}[args.evaluator],
+        "data": "synthetic: self-play from the initial position, games refilled as they end; DualNetwork "
+                + ("random init torch.manual_seed(0) (the reference's initial best.pth)" if args.net == "seed0"
+                   else "with calibrated BatchNorm statistics (tests/golden/netcal.npz)") + "; no checkpoint",
+        "config": {
+            "workload": f"{G} concurrent self-play games per GPU x {S} sims/move, MCTS_BATCH_SIZE {B}, "
+                        f"tau 1.0, continuous self-play (finished games refilled; population aged "
+                        f"{args.age} moves before warmup); one step = one move of every game",
+            "games_per_gpu": G, "sims_per_move": S, "mcts_batch_size": B, "aged_moves": args.age,
+            "eval_cache_log2": args.cache_log2, "eval_cache_clear_every": args.cache_clear_every,
+            "lanes_per_gpu": args.lanes,
+            "evaluator": {"fused": "DualNetwork 128f x16 on HIP kernels: stem from bitboards, residual tower as "
+                                   "fused Winograd F(3x3,3x3) convs (csrc/wino3h_conv.hip, split-f16 MFMA, f32 "
+                                   "accumulation, per-board scaling), heads (csrc/nn_kernels.hip)",
+                          "fused_f16": "DualNetwork 128f x16 on HIP kernels in the optional f16 mode: the "
+                                       "Winograd tower conv with one f16 MFMA product per point "
+                                       "(uttt_nn_conv3x3_wino3h_f16)",
+                          "nn": "DualNetwork 128f x16 fp32, BN folded, PyTorch-ROCm/MIOpen",
+                          "hash": "device hash evaluator (no network)"}[args.evaluator],
+            "parallelism": f"games sharded over {world} GPU(s) by contiguous global-id blocks, "
+                           f"no data-path collective",
+        },
+        "full": bool(args.full),
+    }
+
+
 def main():
     args = parse()
     if args.cpu_baseline_child:
@@ -622,13 +753,19 @@ def main():
     # the measurement: K steps with no per-dispatch events in the timed region; then a separate instrumented
     # pass (every kernel timed by its own dispatch's events, the network's forwards by events) whose statistics
     # give the rooflines and breakdowns (UTTT_BENCH_ONE_PASS=1: one instrumented pass gives both, as in round 4)
-    one_pass = os.environ.get("UTTT_BENCH_ONE_PASS", "0") == "1"
+    # A plain run stops after the timed steps: the instrumented pass and all that follows need --full.
+    one_pass = args.full and os.environ.get("UTTT_BENCH_ONE_PASS", "0") == "1"
     r_val = run_config(net0, local, rank, world, G, S, B, args.lanes, args.cache_log2, args.age, args.warmup,
-                       args.steps, args.evaluator, args.cache_clear_every, instrument=one_pass)
+                       args.steps, args.evaluator, args.cache_clear_every, instrument=one_pass,
+                       dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r_val.pop("outputs"), rank, world)
     inst_steps = args.steps if one_pass else min(args.steps, 10)
-    r = r_val if one_pass else run_config(net0, local, rank, world, G, S, B, args.lanes, args.cache_log2, args.age,
-                                          min(args.warmup, 2), inst_steps, args.evaluator, args.cache_clear_every,
-                                          instrument=True)
+    r = None
+    if args.full:
+        r = r_val if one_pass else run_config(net0, local, rank, world, G, S, B, args.lanes, args.cache_log2,
+                                              args.age, min(args.warmup, 2), inst_steps, args.evaluator,
+                                              args.cache_clear_every, instrument=True)
 
     tot = torch.tensor([float(r_val["sims"]), r_val["elapsed"]], dtype=torch.float64,
                        device="cpu" if args.rehearse_shared_gpu else dev)
@@ -641,7 +778,7 @@ def main():
     total_sims, max_elapsed = float(tot[0].item()), float(tot[1].item())
 
     variants = None
-    if world == 1 and not args.no_variants and args.evaluator.startswith("fused"):
+    if args.full and world == 1 and not args.no_variants and args.evaluator.startswith("fused"):
         variants = {}
         for key, kw in (("calibrated_net", dict(net=calibrated_network(NETCAL, dev))),
                         ("cache_off", dict(cache_log2=0)),
@@ -710,13 +847,18 @@ def main():
             variants[key] = sv
 
     iso = None
-    if world == 1 and not args.no_isolated and r["conv"] == "wino3h" and r["tower"]:
+    if args.full and world == 1 and not args.no_isolated and r["conv"] == "wino3h" and r["tower"]:
         nb = round(sum(n for n, _ in r["tower"]) / len(r["tower"]))
         iso = isolated_conv(net0, [nb, 16384])
         # the optional dataflow tower alone (the two-lane headline keeps the per-conv launches: DESIGN §5)
         iso["tower_dataflow"] = isolated_tower(net0, [nb, 16384])
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        out = headline(args, world, total_sims / max_elapsed, max_elapsed)
+        if args.rehearse_shared_gpu:
+            out["config"]["rehearsal"] = f"{world} ranks sharing one GPU over gloo (not a scaling measurement)"
+        print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
         value = total_sims / max_elapsed
         st = r["stats"]
         flops_direct = NN_FLOP_PER_STATE * r["rows"]
@@ -734,43 +876,8 @@ def main():
         pmc_sel = "pmc_select_tree.json" if tree else "pmc_select.json"
         pmc_app = "pmc_apply_tree.json" if tree else "pmc_apply.json"
         tree_rf = tree_rooflines(st, r["trees_per_launch"], args.evaluator, S, pmc_sel, pmc_app)
-        out = {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "simulations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(max_elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"fused": "f32 activations and accumulation; tower point GEMMs as 3-term split-f16 products "
-                               "on the f16 MFMA (f32-level accuracy: within 1e-5 of the reference's fp32 network)",
-                      "fused_f16": "f32 activations and accumulation; tower point GEMMs as ONE f16 product (the "
-                                   "optional f16 mode: ~1e-2 on the network's outputs, not the reference's numerics)",
-                      "nn": "f32", "hash": "f32 (hash evaluator)"}[args.evaluator],
-            "data": "synthetic: self-play from the initial position, games refilled as they end; DualNetwork "
-                    + ("random init torch.manual_seed(0) (the reference's initial best.pth)" if args.net == "seed0"
-                       else "with calibrated BatchNorm statistics (tests/golden/netcal.npz)") + "; no checkpoint",
-            "config": {
-                "workload": f"{G} concurrent self-play games per GPU x {S} sims/move, MCTS_BATCH_SIZE {B}, "
-                            f"tau 1.0, continuous self-play (finished games refilled; population aged "
-                            f"{args.age} moves before warmup); one step = one move of every game",
-                "games_per_gpu": G, "sims_per_move": S, "mcts_batch_size": B, "aged_moves": args.age,
-                "eval_cache_log2": args.cache_log2, "eval_cache_clear_every": args.cache_clear_every,
-                "lanes_per_gpu": args.lanes,
-                "evaluator": {"fused": "DualNetwork 128f x16 on HIP kernels: stem from bitboards, residual tower as "
-                                       "fused Winograd F(3x3,3x3) convs (csrc/wino3h_conv.hip, split-f16 MFMA, f32 "
-                                       "accumulation, per-board scaling), heads (csrc/nn_kernels.hip)",
-                              "fused_f16": "DualNetwork 128f x16 on HIP kernels in the optional f16 mode: the "
-                                           "Winograd tower conv with one f16 MFMA product per point "
-                                           "(uttt_nn_conv3x3_wino3h_f16)",
-                              "nn": "DualNetwork 128f x16 fp32, BN folded, PyTorch-ROCm/MIOpen",
-                              "hash": "device hash evaluator (no network)"}[args.evaluator],
-                "parallelism": f"games sharded over {world} GPU(s) by contiguous global-id blocks, "
-                               f"no data-path collective",
-            },
+        out = headline(args, world, value, max_elapsed)
+        out.update({
             "roofline": conv_roofline(r, inst_steps) if conv else tree_rf[0],
             "roofline_select": dict(tree_rf[0],
                                     latency_model={
@@ -816,7 +923,7 @@ def main():
                                                                                      r["cache"]["misses"], 1), 4),
                                 log2_capacity=args.cache_log2) if r["cache"] else None),
             "variants": variants,
-        }
+        })
         if iso and out.get("roofline") and out["roofline"].get("bound") == "mfma":
             out["roofline"]["isolated"] = iso
         if args.rehearse_shared_gpu:

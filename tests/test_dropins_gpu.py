@@ -190,7 +190,7 @@ def test_bench_multi_rank_path(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--age", "3", "--games", "256",
-           "--rehearse-shared-gpu", "--no-variants", "--no-cpu-baseline"]
+           "--rehearse-shared-gpu", "--full", "--no-variants", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, _failure_text(r)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

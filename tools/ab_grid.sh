@@ -8,7 +8,7 @@ mkdir -p $OUT
 i=0
 for g in ${GRIDS:-1 0.5 1 0.5}; do
   i=$((i + 1))
-  UTTT_WINO3H_GRID=$g timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-variants --no-isolated --steps 10 \
+  UTTT_WINO3H_GRID=$g timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-variants --no-isolated --steps 10 \
     --warmup 4 ${BENCH_ARGS:-} > $OUT/head_${i}_g$g.log 2>&1 || exit $?
   python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(sys.argv[2], d['value'], d['roofline']['avg_launch_us'], d['nn']['frac'])" $OUT/head_${i}_g$g.log $g
 done

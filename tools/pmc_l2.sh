@@ -14,7 +14,7 @@ run() {  # name counters cmd...
   local rc=$?; echo "pass $name ($ctr) rc=$rc"
   [ $rc -eq 0 ] || { tail -5 $OUT/$name.log; exit $rc; }
 }
-BENCH="python3 bench.py --no-cpu-baseline --no-variants --no-isolated --steps 6 --warmup 2 --age 40"
+BENCH="python3 bench.py --full --no-cpu-baseline --no-variants --no-isolated --steps 6 --warmup 2 --age 40"
 run bench_hit "TCC_HIT_sum TCC_MISS_sum" $BENCH
 run fwd_hit "TCC_HIT_sum TCC_MISS_sum" python3 tools/diag/nn_forward_only.py 1344 12
 run bench_fetch "FETCH_SIZE" $BENCH
