@@ -152,11 +152,9 @@ int uttt_search_count_copy(uttt_engine_t *eng, int32_t *dst);
 /* Device address of the round's counts. */
 int uttt_search_count_ptr(uttt_engine_t *eng, const int32_t **count);
 /* uttt_search_select_async whose scan also stores the three counts into slot ring_slot (0..7) of
- * the engine's host-visible count ring (fine-grained pinned memory, system-scope stores): the host
- * reads them once an event recorded after this call has completed, with no copy on the stream. */
-int uttt_search_select_async_to(uttt_engine_t *eng, int32_t ring_slot);
-/* The same, and the scan stores `tag` into word 3 of the slot after the counts (a system-scope release
- * store): the host polls the tag instead of an event (round 5, SelfPlay's network rounds). */
+ * the engine's host-visible count ring (fine-grained pinned memory, system-scope stores), with no copy
+ * on the stream, and then `tag` into word 3 of the slot (a system-scope release store): the host reads
+ * the counts once it has polled the tag there, no event needed (round 5, SelfPlay's network rounds). */
 int uttt_search_select_async_tag(uttt_engine_t *eng, int32_t ring_slot, int32_t tag);
 /* The count ring: *ring = n_slots x {pending, stopped, left after apply, tag} int32, host memory. */
 int uttt_search_count_ring(uttt_engine_t *eng, const int32_t **ring, int32_t *n_slots);
@@ -212,12 +210,13 @@ int uttt_eval_hash(uttt_engine_t *eng, const float *nn_input, int32_t n, float *
 int uttt_eval_hash_dev(uttt_engine_t *eng, float *policy, float *value);
 /* One whole round with the hash evaluator, enqueued by one call (round 5; the rounds of
  * SelfPlay.steps with HashEvaluator lanes, i.e. the kernel microbenchmark of SURVEY §8(d)):
- * uttt_search_select_async_to(ring_slot) -> uttt_eval_hash_dev(policy, value) ->
- * uttt_search_apply(on_device), with the apply staged: the next call runs it and its own select as
- * one launch (k_round: per tree, the previous evaluation applied, then the next descent), and any
- * other call that reads the trees (the move's end, the root results, a synchronous select) applies
- * it first. UTTT_FUSED_ROUNDS=0 launches the three steps as written above. The scan stores the
- * round's counts and then `tag` (word 3 of the slot; the counts' stores drained before it), so the host
+ * uttt_search_select_async_tag(ring_slot, tag) -> uttt_eval_hash_dev(policy, value) ->
+ * uttt_search_apply(on_device), with the apply staged: the next call runs it, its own select and its
+ * own evaluation as one launch (k_round1: per tree, the previous evaluation applied, then the next
+ * descent, then the queued leaf evaluated into the tree's row), and any other call that reads the
+ * trees (the move's end, the root results, a synchronous select) applies it first.
+ * UTTT_FUSED_ROUNDS=0 launches the three steps as written above. The round stores its
+ * counts and then `tag` (word 3 of the slot; the counts' stores drained before it), so the host
  * learns that the counts landed by polling the tag: no event and no host sync per round. policy:
  * (max_trees, 81) f32, value: (max_trees,) f32, device memory, left untouched until the staged apply
  * has run. Replaces, for the test evaluator, one pass of the flush loop of uttt_mcts.cpp:109-167

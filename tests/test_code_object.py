@@ -26,7 +26,6 @@ PRODUCT = {
     "k_finalize": "10k_finalizeE",
     "k_archive": "9k_archiveE",
     "k_flush1<cpp>": "8k_flush1ILb0E",
-    "k_round<cpp>": "7k_roundILb0E",
     # round 6: the one-dispatch hash round and the resident one-tree search (a 48-byte spill in k_round1 was
     # measured slower on the GPU before this guard covered it)
     "k_round1<cpp>": "8k_round1ILb0E",

@@ -7,11 +7,13 @@ recorded and replayed into the oracle so search parity is checked
 independently of network numerics."""
 import os
 import random
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, golden
+from conftest import GOLDEN, PKG, REPO, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -209,6 +211,40 @@ def test_move_loop_in_c_equals_the_python_round_loop(gpu, oracle_lib, monkeypatc
             assert np.array_equal(r["policies"].view(np.uint64), ref[g]["policies"].view(np.uint64)), (loop, g)
         stats[loop] = (per_call, sp.sims, sp.rounds, sp.leaves, sp.finished, sp.moves)
     assert stats["1"] == stats["0"]
+
+
+_UNFUSED_CHILD = """
+import sys
+import numpy as np
+import uttt_amd
+sp = uttt_amd.SelfPlay(6, 30, 4, 1.0, cache_log2=0)
+sp.run(0, int(sys.argv[2]), int(sys.argv[3]))
+recs = sp.records(with_inputs=False)
+np.savez(sys.argv[1], games=np.array([r["game"] for r in recs]), lengths=np.array([len(r["actions"]) for r in recs]),
+         actions=np.concatenate([r["actions"] for r in recs]), policies=np.concatenate([r["policies"] for r in recs]))
+"""
+
+
+def test_unfused_hash_rounds_match_the_oracle(gpu, oracle_lib, tmp_path):
+    """UTTT_FUSED_ROUNDS=0 (read once per process, so a fresh child): each hash round is the public calls'
+    select + scan, hash evaluation and apply, nothing is staged (flush_dev_apply finds nothing at the move's
+    end), and the C move loop waits on the ring slot's tag. One lane; records equal the oracle's bit for bit."""
+    n_games, seed = 8, 515
+    ref = [oracle_lib.self_play_game_hash(seed + g, 1.0, 30, 4) for g in range(n_games)]
+    out = str(tmp_path / "unfused.npz")
+    env = dict(os.environ, UTTT_FUSED_ROUNDS="0", PYTHONPATH=os.pathsep.join((REPO, PKG)))
+    r = subprocess.run([sys.executable, "-c", _UNFUSED_CHILD, out, str(n_games), str(seed)], capture_output=True,
+                       text=True, env=env, timeout=60, cwd=REPO)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    with np.load(out) as z:
+        games, lengths, actions, policies = z["games"], z["lengths"], z["actions"], z["policies"]
+    assert games.tolist() == list(range(n_games))
+    off = 0
+    for g, n in enumerate(lengths.tolist()):
+        assert np.array_equal(actions[off:off + n], ref[g]["actions"].astype(np.int64)), g
+        assert np.array_equal(policies[off:off + n].view(np.uint64), ref[g]["policies"].view(np.uint64)), g
+        off += n
+    assert off == len(actions)
 
 
 @pytest.mark.parametrize("budget", ["1", "3"])

@@ -137,7 +137,7 @@ struct Pool {
 };
 constexpr int kMaxSimsRec = UTTT_MAX_SIMS;
 static_assert(82 + 81ll * kMaxSimsRec < (1ll << 20), "first-child index: 20 bits");
-constexpr int kCountRing = 8;  // host-visible count slots per engine (uttt_search_select_async_to)
+constexpr int kCountRing = 8;  // host-visible count slots per engine (uttt_search_select_async_tag, uttt_round_hash_async)
 
 struct Trees {
     TreeCtl *ctl;
@@ -151,7 +151,6 @@ struct Trees {
                       // tree has simulations left after it) | the leaf's depth << 8
     int32_t *tree_of; // [slot]
     int32_t *depth_of; // [slot]: the queued leaf's depth (k_apply loads only the path entries it uses)
-    int32_t *slot_of;  // [tree]: its queued leaf's slot this round, -1 for none (k_round: apply by tree)
     int32_t *count;   // [0] pending leaves this round, [1] trees stopped by the select budget,
                       // [2] trees with simulations left after this round's apply
     int32_t n_trees;
@@ -1304,10 +1303,7 @@ __global__ __launch_bounds__(1024) void k_scan(Trees tr, unsigned long long *sta
         const int p = i - b < kScanPer ? held[i - b] : tr.pending[i];
         if ((p & 1) != 0) {  // 1 or 3
             tr.depth_of[slot] = p >> 8;
-            tr.slot_of[i] = slot;
             tr.tree_of[slot++] = i;
-        } else {
-            tr.slot_of[i] = -1;
         }
     }
     if (tid == 0) {
@@ -1640,43 +1636,63 @@ __global__ __launch_bounds__(kWave) void k_flush1(Pool pool, Trees tr, EvalCache
     select_wave<PY>(pool, tr, cache, stats, 0, s_row, host_leaf, tag);
 }
 
-// One round of many trees in one launch (round 5, uttt_round_hash_async): wave t applies its tree's
-// evaluation of the previous round (k_apply's body, the slot from k_scan's slot_of) and then runs the
-// tree's next descent (k_select's body). Trees are independent but for the evaluation cache, whose
-// versioned records make a probe racing another tree's insert see either the old or the new record, and a
-// hit or a miss give the same tree (a miss is evaluated later with the same values). One dispatch where
-// k_apply and k_select took two.
-template <bool PY>
-__global__ __launch_bounds__(kBlock, 4) void k_round(Pool pool, Trees tr, EvalCache cache,
-                                                  const float *__restrict__ policy, int64_t pld,
-                                                  const float *__restrict__ value, int64_t vld,
-                                                  unsigned long long *stats) {
-    __shared__ __attribute__((aligned(16))) float s_row[kWavesPerBlock][84];
-    const int t = wave_index();
-    if (t >= tr.n_trees) return;
-    const int slot = __builtin_amdgcn_readfirstlane(tr.slot_of[t]);
-    if (slot >= 0) {
-        apply_wave(pool, tr, cache, policy, pld, value, vld, nullptr, 0, stats ? stats + kKApply * kRow : nullptr,
-                   slot, s_row[threadIdx.x >> 6]);
-        wave_memory_fence();  // the descent reads the records the apply wrote
+// The hash evaluator's outputs for one state into row `row` (k_hash_leaves' and k_round1's): bit j = ch * 81 +
+// R * 9 + C of the network input, as k_encode writes it, so the words and outputs are k_hash_eval's.
+__device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__restrict__ policy, float *__restrict__ value,
+                                              int row) {
+    const int lane = lane_id();
+    uint32_t m[3];
+    legal_mask(s, m);
+    uint64_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = i * 64 + lane;
+        bool on = false;
+        if (j < 243) {
+            const int ch = j / 81, a = action_at(j % 81);
+            on = (ch == 0 ? bit_of(s.own, a) : (ch == 1 ? bit_of(s.opp, a) : bit_of(m, a))) != 0u;
+        }
+        w[i] = __ballot(on);
     }
-    select_wave<PY>(pool, tr, cache, stats, t, s_row[threadIdx.x >> 6], nullptr, 0);
+    const uint64_t h = hash_words(w);
+    policy[(size_t)row * 81 + lane] = hash_prior(h, lane);
+    if (lane < 17) policy[(size_t)row * 81 + 64 + lane] = hash_prior(h, 64 + lane);
+    if (lane == 0) value[row] = hash_value(h);
 }
 
-// The hash evaluator's outputs for one state into row `row` (k_hash_leaves' body): bit j = ch * 81 + R * 9 + C
-// of the network input, as k_encode writes it, so the words and outputs are k_hash_eval's.
-__device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__restrict__ policy, float *__restrict__ value,
-                                              int row);
+// The select's slowest tree folded into the sums (as k_scan folds it): the max over the stripes of rows rm and
+// rt, one stripe per lane l of one wave, which clears them
+__device__ __forceinline__ void fold_select_max(unsigned long long *stats, int rm, int rt, int l) {
+    unsigned long long ml = 0ull, mt = 0ull;
+    if (l < kStripes) {
+        unsigned long long *a = stats + rm * kRow + l * kStripeStride;
+        unsigned long long *bb = stats + rt * kRow + l * kStripeStride;
+        ml = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        mt = __hip_atomic_load(bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(bb, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long ol = __shfl_xor(ml, off), ot = __shfl_xor(mt, off);
+        ml = ol > ml ? ol : ml;
+        mt = ot > mt ? ot : mt;
+    }
+    if (l == 0) {
+        stats[kKSelMaxSum * kRow] += ml;
+        stats[kKSelTripMaxSum * kRow] += mt;
+    }
+}
 
-// One tree-only round in ONE dispatch (round 6; UTTT_ROUND_DISPATCHES=3 keeps k_round +
-// k_scan + k_hash_leaves). With the hash evaluator nothing needs the leaves in slot order, so the rows are
-// indexed by TREE: wave t applies its tree's evaluation of the previous round from row t (apply != 0 and its
-// pending word, still the previous round's, shows a queued leaf), runs the next descent (k_select's body), and
-// evaluates the leaf it queued straight into row t. The round's counts, which k_scan produced, are summed
-// per block into a partial (sc1 store) and the last block to arrive (striped arrival counters, then one top
-// counter) adds the partials, publishes them (device counts, the host ring and its tag) and resets the
-// counters for the next round. Every tree's work is k_round's in the same order, so every result is the
-// three-dispatch round's (the fused-rounds test runs both).
+// One tree-only round in ONE dispatch (round 6; UTTT_FUSED_ROUNDS=0 keeps the public calls'
+// k_select + k_scan + k_hash_leaves + k_apply). With the hash evaluator nothing needs the leaves in slot order,
+// so the rows are indexed by TREE: wave t applies its tree's evaluation of the previous round from row t
+// (apply != 0 and its pending word, still the previous round's, shows a queued leaf), runs the next descent
+// (k_select's body), and evaluates the leaf it queued straight into row t. The round's counts, which k_scan
+// produces for the other rounds, are summed per block into a partial (sc1 store) and the last block to arrive
+// (striped arrival counters, then one top counter) adds the partials, publishes them (device counts, the host
+// ring and its tag) and resets the counters for the next round. Every tree's work is k_apply's and k_select's
+// in the same order, so every result is the unfused round's (the fused-rounds test runs both).
 constexpr int kR1Stripes = 8;
 // uttt_rounds_hash_move's per-block count words: n0 (queued leaves) bits 0-4, n1 (budget stops) 5-9, n2
 // (trees with simulations left) 10-14, at most kWavesPerBlock = 16 each; the round's tag (17 bits) above
@@ -1703,26 +1719,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_round1(Pool pool, Trees tr, EvalC
         if (stats && blockIdx.x == 0 && threadIdx.x < kWave) {
             // the previous round's slowest tree (the other parity's rows) into the sums; this round's waves
             // write this parity's rows meanwhile
-            const int rm = stats_parity ? kKSelMax : kKSelMaxB, rt = stats_parity ? kKSelTripMax : kKSelTripMaxB;
-            unsigned long long ml = 0ull, mt = 0ull;
-            if (threadIdx.x < kStripes) {
-                unsigned long long *a = stats + rm * kRow + threadIdx.x * kStripeStride;
-                unsigned long long *bb = stats + rt * kRow + threadIdx.x * kStripeStride;
-                ml = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                mt = __hip_atomic_load(bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(bb, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long ol = __shfl_xor(ml, off), ot = __shfl_xor(mt, off);
-                ml = ol > ml ? ol : ml;
-                mt = ot > mt ? ot : mt;
-            }
-            if (threadIdx.x == 0) {
-                stats[kKSelMaxSum * kRow] += ml;
-                stats[kKSelTripMaxSum * kRow] += mt;
-            }
+            fold_select_max(stats, stats_parity ? kKSelMax : kKSelMaxB, stats_parity ? kKSelTripMax : kKSelTripMaxB,
+                            (int)threadIdx.x);
         }
         const uint32_t t17 = ((uint32_t)tag & kPartTagMask) << kPartTagShift;
         bool empty = false;
@@ -1825,28 +1823,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_round1(Pool pool, Trees tr, EvalC
         s_sum[2][threadIdx.x >> 6] = c2;
     }
     // the select's slowest tree (as k_scan folds it): the max over the stripes, one per lane of wave 1
-    if (stats && threadIdx.x >= kWave && threadIdx.x < 2 * kWave) {
-        const int l = threadIdx.x - kWave;
-        unsigned long long ml = 0ull, mt = 0ull;
-        if (l < kStripes) {
-            unsigned long long *a = stats + kKSelMax * kRow + l * kStripeStride;
-            unsigned long long *bb = stats + kKSelTripMax * kRow + l * kStripeStride;
-            ml = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            mt = __hip_atomic_load(bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(bb, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long ol = __shfl_xor(ml, off), ot = __shfl_xor(mt, off);
-            ml = ol > ml ? ol : ml;
-            mt = ot > mt ? ot : mt;
-        }
-        if (l == 0) {
-            stats[kKSelMaxSum * kRow] += ml;
-            stats[kKSelTripMaxSum * kRow] += mt;
-        }
-    }
+    if (stats && threadIdx.x >= kWave && threadIdx.x < 2 * kWave)
+        fold_select_max(stats, kKSelMax, kKSelTripMax, (int)threadIdx.x - kWave);
     __syncthreads();
     if (threadIdx.x == 0) {
         int n0 = 0, n1 = 0, n2 = 0;
@@ -1952,28 +1930,6 @@ __global__ __launch_bounds__(kBlock) void k_hash_leaves(Trees tr, float *__restr
     if (row >= tr.count[0]) return;
     const uttt_state_t s = tr.leaf[tr.tree_of[row]];
     hash_leaf_row(s, policy, value, row);
-}
-
-__device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__restrict__ policy, float *__restrict__ value,
-                                              int row) {
-    const int lane = lane_id();
-    uint32_t m[3];
-    legal_mask(s, m);
-    uint64_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j = i * 64 + lane;
-        bool on = false;
-        if (j < 243) {
-            const int ch = j / 81, a = action_at(j % 81);
-            on = (ch == 0 ? bit_of(s.own, a) : (ch == 1 ? bit_of(s.opp, a) : bit_of(m, a))) != 0u;
-        }
-        w[i] = __ballot(on);
-    }
-    const uint64_t h = hash_words(w);
-    policy[(size_t)row * 81 + lane] = hash_prior(h, lane);
-    if (lane < 17) policy[(size_t)row * 81 + 64 + lane] = hash_prior(h, 64 + lane);
-    if (lane == 0) value[row] = hash_value(h);
 }
 
 __global__ void k_root_visits(Pool pool, Trees tr, int32_t *visits, int32_t *n_legal) {
@@ -2630,10 +2586,7 @@ __device__ __forceinline__ void mt_seed_wave(uint32_t *key, int32_t *pos, uint32
 // Each block: the slots of k_finalize's work list (entry w, w + grid, ...; round 6, in place of a workgroup
 // per slot). A finished game's plies are copied with eight independent loads in flight per thread before
 // their stores (round 4: one dependent load-store pair per iteration, ~19 memory round trips per game, a
-// 39 us launch). seed: the last wave also seeds a refilled slot's key (selfplay_begin and the blocking move
-// end, and the asynchronous one by default); UTTT_SEED_STREAM=1 runs the whole kernel on the engine's side
-// stream, off the critical path (a key is first drawn from, and a finished game's rows first overwritten, at
-// the next move's end).
+// 39 us launch). seed: the last wave also seeds a refilled slot's key (selfplay_begin and both move ends).
 constexpr int kArchiveBlocks = 256;
 __global__ __launch_bounds__(256) void k_archive(SelfPlay sp, const unsigned long long *err, int seed) {
     // the failure word, the list's length and this block's first entry are loaded together (the grid is at
@@ -2709,11 +2662,11 @@ struct uttt_engine {
     float *h_eval = nullptr;     // fine-grained pinned: its evaluation, read by k_apply (uttt_search_apply_host):
                                  // [rows][96] policy, [rows] value, one int32 0 (the per-copy row base)
     int64_t h_eval_rows = 0;
-    // a hash round's evaluation staged by uttt_round_hash_async, applied by the next round's k_round (or by
-    // flush_dev_apply before any other call that reads the trees); UTTT_FUSED_ROUNDS=0: separate launches
+    // a hash round's evaluation staged by uttt_round_hash_async (rows by tree), applied by the next round's
+    // k_round1 (or by flush_dev_apply before any other call that reads the trees); UTTT_FUSED_ROUNDS=0: separate
+    // launches, nothing staged
     const float *dev_apply_policy = nullptr, *dev_apply_value = nullptr;
     bool dev_apply_staged = false;
-    bool dev_apply_by_tree = false;  // staged by a one-dispatch round (k_round1): rows by tree, no scan
     // the resident one-tree search (uttt_search1_*, k_search1): its host block and evaluation rows
     Search1Host *h_s1 = nullptr;  // fine-grained pinned: Search1Host, then policy [cap][96], value [cap]
     int32_t s1_cap = 0, s1_seq = 0;
@@ -2763,11 +2716,6 @@ struct uttt_engine {
     };
     std::vector<Ev> pending_ev;
     std::vector<hipEvent_t> ev_pool;
-    // the asynchronous move end's side stream (UTTT_SEED_STREAM=1): k_archive runs there behind
-    // k_finalize (ev_fin) and the next move end waits for it (ev_seed, join_seed)
-    hipStream_t seed_stream = nullptr;
-    hipEvent_t ev_fin = nullptr, ev_seed = nullptr;
-    bool seed_inflight = false;
     double ms[kKernelCount] = {};
     int64_t launches[kKernelCount] = {};
     std::vector<void *> allocs;
@@ -2964,7 +2912,7 @@ int uttt_engine_create(int32_t device, int32_t max_trees, int32_t max_sims, uttt
         (rc = alloc_n(e, &e->tr.path, (size_t)max_trees * kMaxDepth)) ||
         (rc = alloc_n(e, &e->tr.path_rec, (size_t)max_trees * kMaxDepth)) || (rc = alloc_n(e, &e->tr.pending, max_trees)) ||
         (rc = alloc_n(e, &e->tr.tree_of, max_trees)) || (rc = alloc_n(e, &e->tr.depth_of, max_trees)) ||
-        (rc = alloc_n(e, &e->tr.slot_of, max_trees)) || (rc = alloc_n(e, &e->tr.count, 4)) ||
+        (rc = alloc_n(e, &e->tr.count, 4)) ||
         (rc = alloc_n(e, &e->d_scores, (size_t)max_trees * 81)) || (rc = alloc_n(e, &e->d_visits, (size_t)max_trees * 81)) ||
         (rc = alloc_n(e, &e->d_nlegal, max_trees)) || (rc = alloc_n(e, &e->d_bytes, kKernelCount * kRow)) ||
         (rc = alloc_n(e, &e->d_cache_ctr, 4 * kRow)) ||
@@ -3010,10 +2958,6 @@ int uttt_engine_destroy(uttt_engine_t *e) {
     (void)search1_stop(e);  // a resident one-tree search wave exits first
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     drain_events(e);
-    if (e->seed_stream) (void)hipStreamSynchronize(e->seed_stream);
-    if (e->ev_fin) (void)hipEventDestroy(e->ev_fin);
-    if (e->ev_seed) (void)hipEventDestroy(e->ev_seed);
-    if (e->seed_stream) (void)hipStreamDestroy(e->seed_stream);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->d_pol_scratch) (void)hipFree(e->d_pol_scratch);
@@ -3052,7 +2996,6 @@ int uttt_engine_set_stream(uttt_engine_t *e, void *stream) {
 
 int64_t uttt_engine_device_bytes(const uttt_engine_t *e) { return e ? e->bytes : 0; }
 
-static int search1_stop(uttt_engine *e);
 static int search_begin_common(uttt_engine *e, int32_t n_trees, int32_t sims, int32_t batch) {
     if (int rc0 = search1_stop(e)) return rc0;  // a resident one-tree search left unfinished
     e->dev_apply_staged = false;  // a staged round of a search that was never ended is dropped with it
@@ -3144,14 +3087,6 @@ int uttt_search_select(uttt_engine_t *e, float *nn_input, int32_t *n_pending) {
 
 static int select_async_impl(uttt_engine_t *e, int32_t *host_count, int32_t tag = 0);
 int uttt_search_select_async(uttt_engine_t *e) { return select_async_impl(e, nullptr); }
-
-int uttt_search_select_async_to(uttt_engine_t *e, int32_t ring_slot) {
-    if (!e || ring_slot < 0 || ring_slot >= kCountRing) {
-        set_error("uttt_search_select_async_to: ring slot must be in 0..%d", kCountRing - 1);
-        return UTTT_ERR_ARG;
-    }
-    return select_async_impl(e, e->h_ring + 4 * ring_slot);
-}
 
 int uttt_search_select_async_tag(uttt_engine_t *e, int32_t ring_slot, int32_t tag) {
     if (!e || ring_slot < 0 || ring_slot >= kCountRing) {
@@ -3265,21 +3200,13 @@ static HostApplyArgs host_apply_args(uttt_engine *e) {
     return a;
 }
 
-// A round's evaluation staged by uttt_round_hash_async that no k_round has applied yet, applied now (by
-// every call that reads, selects in or restarts the trees, uttt_search_select_host included)
+// A round's evaluation staged by uttt_round_hash_async (rows by tree) that no k_round1 has applied yet, applied
+// now (by every call that reads, selects in or restarts the trees, uttt_search_select_host included)
 static int flush_dev_apply(uttt_engine *e) {
     if (!e->dev_apply_staged) return UTTT_OK;
     e->dev_apply_staged = false;
-    if (e->dev_apply_by_tree) {  // a one-dispatch round's rows, by tree
-        e->dev_apply_by_tree = false;
-        timed_launch(e, kKApply, k_apply_tree, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->pool, e->tr, e->cache,
-                     e->dev_apply_policy, e->dev_apply_value, bytes_ptr(e, kKApply));
-        return check_launch();
-    }
-    // the phase-3 form of uttt_search_apply: every tree's wave, the count read on the device
-    timed_launch(e, kKApply, k_apply, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->pool, e->tr, e->cache,
-                 e->dev_apply_policy, (int64_t)81, e->dev_apply_value, (int64_t)1, (const int32_t *)nullptr, 0,
-                 bytes_ptr(e, kKApply));
+    timed_launch(e, kKApply, k_apply_tree, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->pool, e->tr, e->cache,
+                 e->dev_apply_policy, e->dev_apply_value, bytes_ptr(e, kKApply));
     return check_launch();
 }
 
@@ -3625,21 +3552,56 @@ int uttt_eval_hash_dev(uttt_engine_t *e, float *policy, float *value) {
     return check_launch();
 }
 
-// the first round after a begin (nothing staged): the plain select, then this round's evaluation staged
-static int select_async_then_stage(uttt_engine *e, int32_t ring_slot, int32_t tag, float *policy, float *value) {
-    int rc = select_async_impl(e, e->h_ring + 4 * ring_slot, tag);
-    if (rc) return rc;
-    if ((rc = uttt_eval_hash_dev(e, policy, value))) return rc;
+static bool fused_rounds() {  // k_round1 (UTTT_FUSED_ROUNDS=0: the public calls' launches)
+    static const bool fuse = [] {
+        const char *v = getenv("UTTT_FUSED_ROUNDS");
+        return !(v && v[0] == '0');
+    }();
+    return fuse;
+}
+
+// part_host != nullptr (uttt_rounds_hash_move only, with the fused rounds): the round's counts go to per-block
+// words instead of the ring slot (k_round1's part_host form)
+static int round_hash_async_impl(uttt_engine *e, int32_t ring_slot, int32_t tag, float *policy, float *value,
+                                 uint32_t *part_host, uint32_t *part_dev, const uint32_t *part_prev, int nb_prev,
+                                 int stats_parity) {
+    if (!e || !policy || !value || ring_slot < 0 || ring_slot >= kCountRing) {
+        set_error("uttt_round_hash_async: bad arguments (ring slot must be in 0..%d)", kCountRing - 1);
+        return UTTT_ERR_ARG;
+    }
+    if (!fused_rounds()) {
+        int rc = select_async_impl(e, e->h_ring + 4 * ring_slot, tag);
+        if (rc) return rc;
+        if ((rc = uttt_eval_hash_dev(e, policy, value))) return rc;
+        return uttt_search_apply(e, policy, 81, value, 1, 0, 1);
+    }
+    // the whole round in one dispatch (k_round1): the previous round's apply, this round's select and its
+    // evaluation, which is staged for the next round
+    if (e->phase != 1) {
+        set_error("uttt_round_hash_async: call uttt_search_begin (or apply the previous round) first");
+        return UTTT_ERR_ORDER;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->host_apply_rows) {  // (a one-tree host evaluation cannot be staged beside a round's)
+        if (int rc0 = flush_host_apply(e)) return rc0;
+    }
+    const int apply = e->dev_apply_staged ? 1 : 0;
+    timed_launch(e, kKSelect, e->tr.py ? k_round1<true> : k_round1<false>, dim3(grid_waves(e->tr.n_trees)),
+                 dim3(kBlock), e->pool, e->tr, e->cache, e->dev_apply_policy, e->dev_apply_value, policy, value, apply,
+                 e->timing ? e->d_bytes : nullptr, e->h_ring + 4 * ring_slot, tag, e->d_r1ctl, part_host, part_dev,
+                 part_prev, nb_prev, stats_parity);
+    if (int rc0 = check_launch()) return rc0;
     e->dev_apply_policy = policy;
     e->dev_apply_value = value;
     e->dev_apply_staged = true;
-    e->dev_apply_by_tree = false;
     e->phase = 1;
     e->n_pending = 0;
     return UTTT_OK;
 }
 
-int uttt_round_hash_async(uttt_engine_t *e, int32_t ring_slot, int32_t tag, float *policy, float *value);
+int uttt_round_hash_async(uttt_engine_t *e, int32_t ring_slot, int32_t tag, float *policy, float *value) {
+    return round_hash_async_impl(e, ring_slot, tag, policy, value, nullptr, nullptr, nullptr, 0, 0);
+}
 
 int uttt_rounds_hash_async(uttt_engine_t *e, int32_t ring_slot, int32_t tag, float *policy, float *value,
                            int32_t n_rounds) {
@@ -3652,18 +3614,6 @@ int uttt_rounds_hash_async(uttt_engine_t *e, int32_t ring_slot, int32_t tag, flo
     return UTTT_OK;
 }
 
-static int round_hash_async_impl(uttt_engine *e, int32_t ring_slot, int32_t tag, float *policy, float *value,
-                                 uint32_t *part_host, uint32_t *part_dev, const uint32_t *part_prev, int nb_prev,
-                                 int stats_parity = 0);
-
-static bool one_dispatch_rounds() {  // k_round1 (UTTT_ROUND_DISPATCHES=3 / UTTT_FUSED_ROUNDS=0: the round-5 forms)
-    static const bool one = [] {
-        const char *f = getenv("UTTT_FUSED_ROUNDS"), *d = getenv("UTTT_ROUND_DISPATCHES");
-        return !(f && f[0] == '0') && !(d && d[0] == '3');
-    }();
-    return one;
-}
-
 int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, float *policy, float *value, int32_t depth,
                           int32_t *n_rounds, int64_t *n_leaves, int32_t *n_with_leaves) {
     if (!e || !n_rounds || !n_leaves || !n_with_leaves || depth < 1 || depth >= kCountRing || ring_slot < 0 ||
@@ -3672,14 +3622,10 @@ int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, floa
                   kCountRing - 1);
         return UTTT_ERR_ARG;
     }
-    // per-block count words (k_round1's part_host form: no last-block publish; UTTT_ROUND_PARTS=0 keeps the ring
+    // per-block count words (k_round1's part_host form: no last-block publish; the unfused rounds keep the ring
     // slot's counts); with kernel timing, each round folds the previous round's select statistics (rows by
     // round parity) at its start
-    static const bool parts_env = [] {
-        const char *v = getenv("UTTT_ROUND_PARTS");
-        return !(v && v[0] == '0');
-    }();
-    const bool parts = parts_env && one_dispatch_rounds();
+    const bool parts = fused_rounds();
     const int nb = grid_waves(e->tr.n_trees);
     if (parts && !e->h_part) {
         const int cap = grid_waves(e->max_trees);
@@ -3782,88 +3728,6 @@ int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, floa
     }
 }
 
-int uttt_round_hash_async(uttt_engine_t *e, int32_t ring_slot, int32_t tag, float *policy, float *value) {
-    return round_hash_async_impl(e, ring_slot, tag, policy, value, nullptr, nullptr, nullptr, 0);
-}
-
-// part_host != nullptr (uttt_rounds_hash_move only, with the one-dispatch rounds): the round's counts go to
-// per-block words instead of the ring slot (k_round1's part_host form)
-static int round_hash_async_impl(uttt_engine *e, int32_t ring_slot, int32_t tag, float *policy, float *value,
-                                 uint32_t *part_host, uint32_t *part_dev, const uint32_t *part_prev, int nb_prev,
-                                 int stats_parity) {
-    if (!e || !policy || !value || ring_slot < 0 || ring_slot >= kCountRing) {
-        set_error("uttt_round_hash_async: bad arguments (ring slot must be in 0..%d)", kCountRing - 1);
-        return UTTT_ERR_ARG;
-    }
-    static const bool fuse = [] {
-        const char *v = getenv("UTTT_FUSED_ROUNDS");
-        return !(v && v[0] == '0');
-    }();
-    // round 6: the whole round in one dispatch (k_round1; UTTT_ROUND_DISPATCHES=3 keeps k_round + k_scan +
-    // k_hash_leaves)
-    if (one_dispatch_rounds()) {
-        if (e->phase != 1) {
-            set_error("uttt_round_hash_async: call uttt_search_begin (or apply the previous round) first");
-            return UTTT_ERR_ORDER;
-        }
-        HIP_TRY(hipSetDevice(e->device));
-        if (e->host_apply_rows) {  // (a one-tree host evaluation cannot be staged beside a round's)
-            if (int rc0 = flush_host_apply(e)) return rc0;
-        }
-        if (e->dev_apply_staged && !e->dev_apply_by_tree)  // staged by a slot-order round: apply it first
-            if (int rc0 = flush_dev_apply(e)) return rc0;
-        const int apply = e->dev_apply_staged ? 1 : 0;
-        timed_launch(e, kKSelect, e->tr.py ? k_round1<true> : k_round1<false>, dim3(grid_waves(e->tr.n_trees)),
-                     dim3(kBlock), e->pool, e->tr, e->cache, e->dev_apply_policy, e->dev_apply_value, policy, value, apply,
-                     e->timing ? e->d_bytes : nullptr, e->h_ring + 4 * ring_slot, tag, e->d_r1ctl, part_host, part_dev,
-                     part_prev, nb_prev, stats_parity);
-        if (int rc0 = check_launch()) return rc0;
-        e->dev_apply_policy = policy;
-        e->dev_apply_value = value;
-        e->dev_apply_staged = true;
-        e->dev_apply_by_tree = true;
-        e->phase = 1;
-        e->n_pending = 0;
-        return UTTT_OK;
-    }
-    if (!fuse) {
-        int rc = select_async_impl(e, e->h_ring + 4 * ring_slot, tag);
-        if (rc) return rc;
-        if ((rc = uttt_eval_hash_dev(e, policy, value))) return rc;
-        return uttt_search_apply(e, policy, 81, value, 1, 0, 1);
-    }
-    // the previous round's apply and this round's select as one k_round launch; this round's apply is staged
-    if (!e->dev_apply_staged) return select_async_then_stage(e, ring_slot, tag, policy, value);
-    if (e->phase != 1) {
-        set_error("uttt_round_hash_async: call uttt_search_begin (or apply the previous round) first");
-        return UTTT_ERR_ORDER;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    if (e->host_apply_rows) {  // (a one-tree host evaluation cannot be staged beside a round's)
-        set_error("uttt_round_hash_async: a host-staged evaluation is pending");
-        return UTTT_ERR_ORDER;
-    }
-    e->dev_apply_staged = false;
-    int rc = 0;
-    timed_launch(e, kKSelect, e->tr.py ? k_round<true> : k_round<false>, dim3(grid_waves(e->tr.n_trees)),
-                 dim3(kBlock), e->pool, e->tr, e->cache, e->dev_apply_policy, (int64_t)81, e->dev_apply_value,
-                 (int64_t)1, e->timing ? e->d_bytes : nullptr);
-    if ((rc = check_launch())) return rc;
-    timed_launch(e, kKScan, k_scan, dim3(1), dim3(1024), e->tr, e->timing ? e->d_bytes : nullptr,
-                 e->h_ring + 4 * ring_slot, tag);
-    if ((rc = check_launch())) return rc;
-    e->n_pending = -1;
-    e->phase = 3;
-    if ((rc = uttt_eval_hash_dev(e, policy, value))) return rc;
-    e->dev_apply_policy = policy;
-    e->dev_apply_value = value;
-    e->dev_apply_staged = true;
-    e->dev_apply_by_tree = false;
-    e->phase = 1;
-    e->n_pending = 0;
-    return UTTT_OK;
-}
-
 static int check_tree_errors(uttt_engine *e) {
     std::vector<TreeCtl> ctl(e->tr.n_trees);
     HIP_TRY(hipMemcpyAsync(ctl.data(), e->tr.ctl, sizeof(TreeCtl) * e->tr.n_trees, hipMemcpyDeviceToHost, e->stream));
@@ -3911,15 +3775,6 @@ int uttt_search_scores(uttt_engine_t *e, float temperature, float *scores, int32
 }
 
 // ----------------------------------------------------------- self-play API --
-// The engine's stream waits for a key seeding still running on the side stream (every self-play call that
-// reads or writes keys, slots or the work list on the stream joins first)
-static int join_seed(uttt_engine *e) {
-    if (!e->seed_inflight) return UTTT_OK;
-    HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_seed, 0));
-    e->seed_inflight = false;
-    return UTTT_OK;
-}
-
 int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, uint32_t seed_base, float temperature,
                         int32_t sims, int32_t batch, int64_t arena_plies) {
     if (!e || game_end < game_begin || game_begin < 0 || arena_plies <= 0) {
@@ -3927,7 +3782,6 @@ int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, 
         return UTTT_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     const int slots = e->max_trees;
     int rc = search_begin_common(e, slots, sims, batch);
     e->tr.py = 0;  // self-play is the cpp/uttt_mcts.cpp path
@@ -3989,7 +3843,6 @@ int uttt_selfplay_move_begin(uttt_engine_t *e, int32_t *n_live) {
         return UTTT_ERR_ORDER;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     const int slots = e->sp.slots;
     e->tr.n_trees = slots;
     if (e->cache.flag && e->cache_clear_every > 0 && e->moves > 0 && e->moves % e->cache_clear_every == 0) {
@@ -4026,7 +3879,6 @@ int uttt_selfplay_move_end(uttt_engine_t *e, int64_t *n_finished) {
         return UTTT_ERR_ORDER;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     if (int rc0 = flush_host_apply(e)) return rc0;  // a staged round's evaluation (uttt_round_hash_async)
     int rc = check_tree_errors(e);
     if (rc) return rc;
@@ -4094,7 +3946,6 @@ int uttt_selfplay_move_end_async(uttt_engine_t *e) {
     }
     HIP_TRY(hipSetDevice(e->device));
     if (int rc0 = flush_host_apply(e)) return rc0;  // a staged round's evaluation (uttt_round_hash_async)
-    if (int rc0 = join_seed(e)) return rc0;         // the previous move end's key seeding
     const int slots = e->sp.slots;
     {  // d_err and the failure flag were reset by this move's k_begin
         TimedLaunch tl(e, kKMoveEnd);
@@ -4107,27 +3958,7 @@ int uttt_selfplay_move_end_async(uttt_engine_t *e) {
                            e->pool, e->sp, fail);
         hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, e->stream, e->sp, fail, (const TreeCtl *)e->tr.ctl,
                            e->d_err, e->h_move);
-        // UTTT_SEED_STREAM=1: k_archive (the finished games' copy to the arena, the refilled slots' keys) runs
-        // on a side stream, overlapping the next move's rounds, which need neither; the next move end and every
-        // reader of the arena or the keys join it (round 6, measured in DESIGN §7)
-        static const bool side = [] {
-            const char *v = getenv("UTTT_SEED_STREAM");
-            return v && v[0] == '1';
-        }();
-        if (side) {
-            if (!e->seed_stream) {
-                HIP_TRY(hipStreamCreateWithFlags(&e->seed_stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_fin, hipEventDisableTiming | hipEventDisableSystemFence));
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_seed, hipEventDisableTiming | hipEventDisableSystemFence));
-            }
-            HIP_TRY(hipEventRecord(e->ev_fin, e->stream));
-            HIP_TRY(hipStreamWaitEvent(e->seed_stream, e->ev_fin, 0));
-            hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->seed_stream, e->sp, err, 1);
-            HIP_TRY(hipEventRecord(e->ev_seed, e->seed_stream));
-            e->seed_inflight = true;
-        } else {
-            hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp, err, 1);
-        }
+        hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp, err, 1);
     }
     int rc = check_launch();
     if (rc) return rc;  // k_finalize stored the counters and the failure word into h_move
@@ -4159,7 +3990,6 @@ int uttt_selfplay_games(uttt_engine_t *e, int64_t *game_ids, int64_t *offsets, i
                         int64_t *n_games) {
     if (!e || !e->selfplay) return UTTT_ERR_ORDER;
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     int64_t ctr[4];
     HIP_TRY(hipMemcpyAsync(ctr, e->sp.ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4181,7 +4011,6 @@ int uttt_selfplay_plies(uttt_engine_t *e, uttt_state_t *states, double *policies
                         float *inputs_hwc, int64_t max_plies, int64_t *n_plies) {
     if (!e || !e->selfplay) return UTTT_ERR_ORDER;
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     const int64_t n = std::min<int64_t>(e->sp_arena_used, max_plies);
     if (n_plies) *n_plies = e->sp_arena_used;
     if (n <= 0) return UTTT_OK;
@@ -4208,7 +4037,6 @@ int uttt_selfplay_plies(uttt_engine_t *e, uttt_state_t *states, double *policies
 int uttt_selfplay_get_rng(uttt_engine_t *e, int32_t slot, uint32_t key[624], int32_t *pos) {
     if (!e || !e->selfplay || slot < 0 || slot >= e->sp.slots || !key || !pos) return UTTT_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     HIP_TRY(hipMemcpyAsync(key, e->sp.mt_key + (size_t)slot * 624, sizeof(uint32_t) * 624, hipMemcpyDeviceToHost,
                            e->stream));
     HIP_TRY(hipMemcpyAsync(pos, e->sp.mt_pos + slot, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -4219,7 +4047,6 @@ int uttt_selfplay_get_rng(uttt_engine_t *e, int32_t slot, uint32_t key[624], int
 int uttt_selfplay_set_rng(uttt_engine_t *e, int32_t slot, const uint32_t key[624], int32_t pos) {
     if (!e || !e->selfplay || slot < 0 || slot >= e->sp.slots || !key || pos < 0 || pos > 624) return UTTT_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc_join = join_seed(e)) return rc_join;
     HIP_TRY(hipMemcpyAsync(e->sp.mt_key + (size_t)slot * 624, key, sizeof(uint32_t) * 624, hipMemcpyHostToDevice,
                            e->stream));
     HIP_TRY(hipMemcpyAsync(e->sp.mt_pos + slot, &pos, sizeof(int32_t), hipMemcpyHostToDevice, e->stream));

@@ -120,20 +120,15 @@ class Engine:
         check(self.lib.uttt_search_select_async(self.h))
         self.n_pending = None
 
-    def select_async_to(self, ring_slot):
-        """select_async whose scan also writes the round's counts into slot ring_slot of the engine's
-        host-visible ring (count_ring()): readable once an event recorded after it has completed."""
-        check(self.lib.uttt_search_select_async_to(self.h, int(ring_slot)))
-        self.n_pending = None
-
     def _next_tag(self):
         """The next ring tag, kept in the int32 range the C ABI takes (a wrapped ctypes value would never
         compare equal to the Python int the waiter holds)."""
         return (getattr(self, "tag", 0) + 1) & 0x7FFFFFFF
 
     def select_async_tag(self, ring_slot):
-        """select_async_to whose scan stores a new tag into word 3 of the ring slot after the counts; returns
-        the tag (the counts are readable once the slot's word 3 holds it)."""
+        """select_async whose scan also writes the round's counts into slot ring_slot of the engine's
+        host-visible ring (count_ring()) and stores a new tag into word 3 of the slot after them; returns the
+        tag (the counts are readable once the slot's word 3 holds it)."""
         self.tag = self._next_tag()
         check(self.lib.uttt_search_select_async_tag(self.h, int(ring_slot), self.tag))
         self.n_pending = None

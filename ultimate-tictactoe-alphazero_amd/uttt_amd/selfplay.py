@@ -330,7 +330,7 @@ class SelfPlay:
                 and getattr(self.lanes[0].evaluator, "round_move", None) is not None
                 and getattr(self.lanes[0].evaluator, "rounds_per_call", 1) == 1):
             return self._steps_move_loop(self.lanes[0], k, depth, progress)
-        spin = depth > 1 and os.environ.get("UTTT_POLL_SLEEP", "0") != "1"
+        spin = depth > 1
         for ln in self.lanes:
             if ln.count_ring is None:
                 ln.count_ring = ln.engine.count_ring()  # the scan writes each round's counts here
@@ -362,7 +362,7 @@ class SelfPlay:
             ready = [key for key in state if state[key][1][0][1].query()]
             if not ready:
                 # cheap rounds (the hash evaluator, ~30 us each): spin, since a 20-us sleep lasts 60-100 us on
-                # Linux and the three rounds in flight drain meanwhile (UTTT_POLL_SLEEP=1 sleeps as before)
+                # Linux and the three rounds in flight drain meanwhile
                 if not spin:
                     time.sleep(2e-5)
                 continue
@@ -519,12 +519,7 @@ class SelfPlay:
         with self._ctx(ln):
             # readiness: the tag the scan stores into the ring slot after the counts (round 5; a torch event
             # per round before)
-            if os.environ.get("UTTT_ROUND_EVENTS") == "1":  # the round-4 form, kept for A/B
-                ln.engine.select_async_to(slot)
-                ready = torch.cuda.Event()
-                ready.record()
-            else:
-                ready = _TagReady(buf, ln.engine.select_async_tag(slot))
+            ready = _TagReady(buf, ln.engine.select_async_tag(slot))
             if spec:
                 p, v = ln.evaluator(None, rc)
                 ln.engine.apply(p, v)
