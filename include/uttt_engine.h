@@ -89,6 +89,13 @@ int uttt_states_input_hwc(const uttt_state_t *s, int64_t n, float *out);
 int uttt_state_to_string(const uttt_state_t *s, char *buf, int32_t cap);
 /* boltzman — cpp/uttt_mcts.cpp:199-216 */
 int uttt_boltzman(const float *xs, int32_t n, float temperature, float *out);
+/* playout — game.py:277-287, for n states, `playouts` (1..4096) uniformly random games from each: wins and
+ * losses of the state's side to move (a lost state: every playout a loss; a drawn one: neither). Python's
+ * `random` is replaced by a counter-based draw keyed by the position's 243 network-input bits and `seed`
+ * (csrc/uttt_playout.h), so playout j is a function of (position, seed, j). Pure CPU: what uttt_playouts and
+ * uttt_eval_playout_dev compute on the device, bit for bit. */
+int uttt_playout_host(const uttt_state_t *states, int64_t n, int32_t playouts, uint64_t seed, int32_t *wins,
+                      int32_t *losses);
 
 /* --------------------------------------------------------------- engine --- */
 typedef struct uttt_engine uttt_engine_t;
@@ -208,6 +215,18 @@ int uttt_eval_hash(uttt_engine_t *eng, const float *nn_input, int32_t n, float *
 /* The same evaluator on the round's pending leaves read from their states, the count read on the
  * device (after uttt_search_select_async): rows [0, count) of policy (81 f32 each) and value. */
 int uttt_eval_hash_dev(uttt_engine_t *eng, float *policy, float *value);
+/* The random-playout evaluator on the round's pending leaves (the count read on the device, as
+ * uttt_eval_hash_dev; after uttt_search_select or uttt_search_select_async): value[row] = (wins - losses) /
+ * playouts of the leaf's side to move over `playouts` (1..4096) playouts (uttt_playout_host), policy row =
+ * 81 x 1.0f, which the apply's legal mask and renormalisation make 1 / |legal|. With it a search is the
+ * batched counterpart of game.py:294-379's mcts_action (PUCT over uniform priors in place of UCB1). A function of the
+ * position and the seed alone, so exact under the evaluation cache. */
+int uttt_eval_playout_dev(uttt_engine_t *eng, int32_t playouts, uint64_t seed, float *policy, float *value);
+/* uttt_playout_host on the device, one wave per state (game.py:277-287 for n states at once; terminal states
+ * included): copies the states in, runs on the engine's stream, copies the counts out and synchronises.
+ * states, wins, losses: host memory. Independent of any search in progress. */
+int uttt_playouts(uttt_engine_t *eng, const uttt_state_t *states, int32_t n, int32_t playouts, uint64_t seed,
+                  int32_t *wins, int32_t *losses);
 /* One whole round with the hash evaluator, enqueued by one call (round 5; the rounds of
  * SelfPlay.steps with HashEvaluator lanes, i.e. the kernel microbenchmark of SURVEY §8(d)):
  * uttt_search_select_async_tag(ring_slot, tag) -> uttt_eval_hash_dev(policy, value) ->
@@ -310,7 +329,7 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* ------------------------------------------------------------ telemetry --- */
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
-/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval.
+/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

@@ -33,6 +33,7 @@
 
 #include "uttt_bits.h"
 #include "uttt_engine.h"
+#include "uttt_playout.h"
 
 namespace uttt {
 
@@ -87,7 +88,9 @@ enum KernelId {
     kKSelTrips, kKSelTripMax, kKSelTripMaxSum,
     // the slowest-tree rows of odd rounds in uttt_rounds_hash_move's per-block form (k_round1 with part_host):
     // each round folds the previous round's rows at its start, so no round needs a last block
-    kKSelMaxB, kKSelTripMaxB, kKernelCount
+    kKSelMaxB, kKSelTripMaxB,
+    kKPlayout,  // k_playout_leaves / k_playout_states launches
+    kKernelCount
 };
 
 // Device counters are striped: counter i of a row lives in kStripes 128-byte slots, and a workgroup
@@ -1932,6 +1935,70 @@ __global__ __launch_bounds__(kBlock) void k_hash_leaves(Trees tr, float *__restr
     hash_leaf_row(s, policy, value, row);
 }
 
+// ---------------------------------------------------------------- playouts --
+// Random-playout evaluator (uttt_playout.h; game.py:277-287 `playout`, the evaluation of game.py:294-379's
+// mcts_action): one wave per position, lane = playout, ceil(P / 64) passes. The position is wave-uniform; each
+// lane plays its own game on a private copy of the 32-byte state in registers until it ends (at most 81 plies;
+// the wave leaves the loop with its last lane), and a pass's wins and losses are two ballots' popcounts.
+// No LDS, no atomics, no scratch.
+__device__ __forceinline__ void playout_wave(const uttt_state_t &s, int P, uint64_t seed, int32_t &wins, int32_t &losses) {
+    const int lane = lane_id();
+    uint32_t m[3];
+    legal_mask(s, m);
+    uint64_t w[4];  // the input words as hash_leaf_row forms them
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = i * 64 + lane;
+        bool on = false;
+        if (j < 243) {
+            const int ch = j / 81, a = action_at(j % 81);
+            on = (ch == 0 ? bit_of(s.own, a) : (ch == 1 ? bit_of(s.opp, a) : bit_of(m, a))) != 0u;
+        }
+        w[i] = __ballot(on);
+    }
+    const uint64_t h = playout_key(w, seed);
+    wins = losses = 0;
+    for (int base = 0; base < P; base += kWave) {
+        const int j = base + lane;
+        int r = 0;
+        if (j < P) r = playout(s, h, (uint32_t)j);
+        wins += (int32_t)__popcll(__ballot(r > 0));
+        losses += (int32_t)__popcll(__ballot(r < 0));
+    }
+}
+
+// The round's evaluator, shaped like k_hash_leaves (one wave per slot, the count read on the device): the
+// value is the mean playout result; the priors are 81 x 1, which k_apply's legal mask and sequential
+// renormalisation turn into exactly 1 / |legal|.
+__global__ __launch_bounds__(kBlock) void k_playout_leaves(Trees tr, int P, uint64_t seed, float *__restrict__ policy,
+                                                           float *__restrict__ value) {
+    const int row = wave_index();
+    if (row >= tr.count[0]) return;
+    const int lane = lane_id();
+    const uttt_state_t s = tr.leaf[tr.tree_of[row]];
+    int32_t wins, losses;
+    playout_wave(s, P, seed, wins, losses);
+    policy[(size_t)row * 81 + lane] = 1.0f;
+    if (lane < 17) policy[(size_t)row * 81 + 64 + lane] = 1.0f;
+    if (lane == 0) value[row] = playout_value(wins - losses, P);
+}
+
+// Flat Monte-Carlo on arbitrary positions, terminal ones included (a lost position: every playout a loss;
+// a drawn one: neither): wins and losses of the side to move over P playouts, one wave per position.
+__global__ __launch_bounds__(kBlock) void k_playout_states(const uttt_state_t *__restrict__ states, int n, int P,
+                                                           uint64_t seed, int32_t *__restrict__ wins,
+                                                           int32_t *__restrict__ losses) {
+    const int row = wave_index();
+    if (row >= n) return;
+    const uttt_state_t s = states[row];
+    int32_t nw, nl;
+    playout_wave(s, P, seed, nw, nl);
+    if (lane_id() == 0) {
+        wins[row] = nw;
+        losses[row] = nl;
+    }
+}
+
 __global__ void k_root_visits(Pool pool, Trees tr, int32_t *visits, int32_t *n_legal) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= tr.n_trees * 81) return;
@@ -2686,6 +2753,9 @@ struct uttt_engine {
     float *d_pol_scratch = nullptr;
     float *d_val_scratch = nullptr;
     int64_t scratch_rows = 0;
+    uttt_state_t *d_po_states = nullptr;  // uttt_playouts: the positions and their [wins | losses], grown on demand
+    int32_t *d_po_counts = nullptr;
+    int64_t po_rows = 0;
     float *d_scores = nullptr;
     int32_t *d_nlegal = nullptr;
     int32_t *d_visits = nullptr;
@@ -2963,6 +3033,8 @@ int uttt_engine_destroy(uttt_engine_t *e) {
     if (e->d_pol_scratch) (void)hipFree(e->d_pol_scratch);
     if (e->d_val_scratch) (void)hipFree(e->d_val_scratch);
     if (e->d_rowbase) (void)hipFree(e->d_rowbase);
+    if (e->d_po_states) (void)hipFree(e->d_po_states);
+    if (e->d_po_counts) (void)hipFree(e->d_po_counts);
     if (e->cache_owner) {
         if (e->cache.flag) (void)hipFree(e->cache.flag);
         if (e->cache.rec) (void)hipFree(e->cache.rec);
@@ -3550,6 +3622,62 @@ int uttt_eval_hash_dev(uttt_engine_t *e, float *policy, float *value) {
     HIP_TRY(hipSetDevice(e->device));
     timed_launch(e, kKHash, k_hash_leaves, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, policy, value);
     return check_launch();
+}
+
+static int check_playouts(int32_t playouts) {
+    if (playouts < 1 || playouts > kMaxPlayouts) {
+        set_error("playouts must be 1..%d (got %d)", kMaxPlayouts, playouts);
+        return UTTT_ERR_ARG;
+    }
+    return UTTT_OK;
+}
+
+int uttt_eval_playout_dev(uttt_engine_t *e, int32_t playouts, uint64_t seed, float *policy, float *value) {
+    if (!e || !policy || !value) return UTTT_ERR_ARG;
+    if (int rc = check_playouts(playouts)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    timed_launch(e, kKPlayout, k_playout_leaves, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, (int)playouts,
+                 seed, policy, value);
+    return check_launch();
+}
+
+int uttt_playouts(uttt_engine_t *e, const uttt_state_t *states, int32_t n, int32_t playouts, uint64_t seed,
+                  int32_t *wins, int32_t *losses) {
+    if (!e || n < 0 || ((!states || !wins || !losses) && n > 0)) {
+        set_error("uttt_playouts: null pointer or negative count");
+        return UTTT_ERR_ARG;
+    }
+    if (int rc = check_playouts(playouts)) return rc;
+    for (int32_t i = 0; i < n; ++i) {
+        if (states[i].active < -1 || states[i].active > 8) {
+            set_error("active_board must be -1..8 (state %d has %d)", i, states[i].active);
+            return UTTT_ERR_ARG;
+        }
+    }
+    if (n == 0) return UTTT_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (n > e->po_rows) {
+        int64_t rows = e->po_rows ? e->po_rows : 1024;
+        while (rows < n) rows *= 2;
+        if (e->d_po_states) (void)hipFree(e->d_po_states);
+        if (e->d_po_counts) (void)hipFree(e->d_po_counts);
+        e->d_po_states = nullptr;
+        e->d_po_counts = nullptr;
+        e->po_rows = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_po_states, (size_t)rows * sizeof(uttt_state_t)));
+        HIP_TRY(hipMalloc((void **)&e->d_po_counts, (size_t)rows * 2 * sizeof(int32_t)));
+        e->po_rows = rows;
+    }
+    int32_t *d_wins = e->d_po_counts, *d_losses = e->d_po_counts + n;
+    HIP_TRY(hipMemcpyAsync(e->d_po_states, states, sizeof(uttt_state_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    timed_launch(e, kKPlayout, k_playout_states, dim3(grid_waves(n)), dim3(kBlock), (const uttt_state_t *)e->d_po_states,
+                 (int)n, (int)playouts, seed, d_wins, d_losses);
+    if (int rc = check_launch()) return rc;
+    HIP_TRY(hipMemcpyAsync(wins, d_wins, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(losses, d_losses, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    drain_events(e);
+    return UTTT_OK;
 }
 
 static bool fused_rounds() {  // k_round1 (UTTT_FUSED_ROUNDS=0: the public calls' launches)

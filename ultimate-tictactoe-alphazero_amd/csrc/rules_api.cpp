@@ -9,6 +9,7 @@
 
 #include "uttt_bits.h"
 #include "uttt_engine.h"
+#include "uttt_playout.h"
 
 namespace uttt {
 // Last error of the calling thread, for every entry point of the C ABI (uttt_last_error).
@@ -172,6 +173,39 @@ int uttt_boltzman(const float *xs, int32_t n, float temperature, float *out) {
     if (sum > 0)
         for (int i = 0; i < n; ++i) out[i] /= sum;
     return n;
+}
+
+int uttt_playout_host(const uttt_state_t *states, int64_t n, int32_t playouts, uint64_t seed, int32_t *wins,
+                      int32_t *losses) {
+    // game.py:277-287 with the counter-based draw of uttt_playout.h; what k_playout_states computes.
+    if (n < 0 || ((!states || !wins || !losses) && n > 0)) {
+        set_error("uttt_playout_host: null pointer or negative count");
+        return UTTT_ERR_ARG;
+    }
+    if (playouts < 1 || playouts > kMaxPlayouts) {
+        set_error("playouts must be 1..%d (got %d)", kMaxPlayouts, playouts);
+        return UTTT_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (states[i].active < -1 || states[i].active > 8) {
+            set_error("active_board must be -1..8 (state %lld has %d)", (long long)i, states[i].active);
+            return UTTT_ERR_ARG;
+        }
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        uint64_t w[4];
+        input_words(states[i], w);
+        const uint64_t h = playout_key(w, seed);
+        int32_t nw = 0, nl = 0;
+        for (int32_t j = 0; j < playouts; ++j) {
+            const int r = playout(states[i], h, (uint32_t)j);
+            nw += r > 0;
+            nl += r < 0;
+        }
+        wins[i] = nw;
+        losses[i] = nl;
+    }
+    return UTTT_OK;
 }
 
 }  // extern "C"

@@ -2,7 +2,9 @@
 model's PV-MCTS player (pv_mcts.pv_mcts_action at temperature 0, on the MI355X engine with the
 Python-search semantics and the fused HIP evaluator) against the random player, EP_GAME_COUNT
 games alternating the first move, printing "VS_Random <average point>" for the training monitors.
-The alpha-beta and plain-MCTS opponents are disabled in the reference too (:86-93)."""
+The alpha-beta and plain-MCTS opponents are disabled in the reference (:87-95); the plain-MCTS one is
+available here behind EP_VS_MCTS (off by default: the output is the reference's), as a batched search over
+random playouts on the engine (uttt_amd.PlayoutEvaluator), and as mcts_action_factory for single moves."""
 import os
 import random
 import sys
@@ -11,12 +13,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import uttt_cpp  # noqa: E402
+import pv_mcts  # noqa: E402
 from pv_mcts import pv_mcts_action  # noqa: E402
 from uttt_amd import arena  # noqa: E402
 from uttt_amd.model import DualNetwork  # noqa: E402
 
 CPP_GAME_AVAILABLE = True
 EP_GAME_COUNT = 10
+EP_VS_MCTS = False  # also print "VS_MCTS <average point>" (evaluate_best_player.py:93-95, commented out there)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 first_player_point = arena.first_player_point
@@ -26,6 +30,22 @@ def random_action(state):
     """game.py:234-236 (Python's global `random`)."""
     legal_actions = state.legal_actions()
     return legal_actions[random.randint(0, len(legal_actions) - 1)]
+
+
+def mcts_action_factory(evaluate_count=1000, playouts=64, seed=0):
+    """game.py:294-379's mcts_action on the engine: next_action(state) runs one tree of evaluate_count
+    simulations whose leaves are valued by `playouts` random playouts (game.py:277-287; uniform priors, PUCT
+    in place of UCB1) and returns the first legal action with the most root visits (game.py:374-379)."""
+    from uttt_amd.selfplay import PlayoutEvaluator
+    search = arena.PvMcts(1, max(50, evaluate_count))
+    evaluator = PlayoutEvaluator(search.engine, playouts, seed)
+
+    def mcts_action(state):
+        (v,) = search.visits([state], evaluator, evaluate_count, pv_mcts.MCTS_BATCH_SIZE)
+        ns = [int(x) for x in v]
+        return state.legal_actions()[ns.index(max(ns))]
+
+    return mcts_action
 
 
 def play(next_actions):
@@ -56,6 +76,9 @@ def evaluate_best_player():
     model.eval()
     next_pv_mcts_action = pv_mcts_action(model, 0.0)
     point = evaluate_algorithm_of("VS_Random", (next_pv_mcts_action, random_action))
+    if EP_VS_MCTS:
+        print("VS_MCTS", arena.evaluate_vs_playouts(model, EP_GAME_COUNT, evaluate_count=pv_mcts.PV_EVALUATE_COUNT,
+                                                    batch_size=pv_mcts.MCTS_BATCH_SIZE)[0])
     del model
     return point
 

@@ -14,7 +14,7 @@ the reference's play() after np.random.seed(seed_base + g) (same players).
 import numpy as np
 
 from .engine import as_states
-from .selfplay import BatchedSearch, NetworkEvaluator
+from .selfplay import BatchedSearch, NetworkEvaluator, PlayoutEvaluator
 
 
 def scores_from_visits(visits, temperature):
@@ -96,19 +96,12 @@ def model_evaluator(model, max_batch=None, engine=None, kind=None):
     return ModelEvaluator(model)
 
 
-def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0, evaluate_count=50,
-                     batch_size=8, device=None, make_evaluator=None, progress=None):
-    """evaluate_network.py:58-104 with all games concurrent. Game g: model0 moves first when g is
-    even, model1 when odd (:78-82). Returns (model0's average point, per-game first-player points,
-    per-game action lists). make_evaluator(model, engine) -> engine evaluator (default: the model
-    called on the engine's input batch; e.g. nnfast.FusedNetworkEvaluator for a DualNetwork)."""
+def _play_games(searches, evaluators, evaluate_counts, game_count, temperature, seed_base, batch_size, progress):
+    """evaluate_network.py:58-104's games, all concurrent: player m (searches[m], evaluators[m],
+    evaluate_counts[m] simulations per move) moves first in game g when g % 2 == m. Game g draws from
+    RandomState(seed_base + g). Returns (player 0's average point, per-game first-player points, per-game
+    action lists)."""
     import uttt_cpp
-    searches = [PvMcts(game_count, evaluate_count, device) for _ in range(2)]
-    if make_evaluator is None:
-        evaluators = (model_evaluator(model0, game_count, searches[0].engine),
-                      model_evaluator(model1, game_count, searches[1].engine))
-    else:
-        evaluators = (make_evaluator(model0, searches[0].engine), make_evaluator(model1, searches[1].engine))
     states = [uttt_cpp.State() for _ in range(game_count)]
     rngs = [np.random.RandomState(seed_base + g) for g in range(game_count)]
     order = [(0, 1) if g % 2 == 0 else (1, 0) for g in range(game_count)]  # (first player, second player)
@@ -121,7 +114,7 @@ def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0
         for m, idx in enumerate(groups):  # one move per live game per iteration
             if not idx:
                 continue
-            vis = searches[m].visits([states[g] for g in idx], evaluators[m], evaluate_count, batch_size)
+            vis = searches[m].visits([states[g] for g in idx], evaluators[m], evaluate_counts[m], batch_size)
             for g, v in zip(idx, vis):
                 legal = states[g].legal_actions()
                 sc = scores_from_visits(v, temperature)
@@ -135,6 +128,42 @@ def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0
     points = [first_player_point(s) for s in states]
     total = sum(p if g % 2 == 0 else 1 - p for g, p in enumerate(points))
     return total / game_count, points, actions
+
+
+def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0, evaluate_count=50,
+                     batch_size=8, device=None, make_evaluator=None, progress=None):
+    """evaluate_network.py:58-104 with all games concurrent. Game g: model0 moves first when g is
+    even, model1 when odd (:78-82). Returns (model0's average point, per-game first-player points,
+    per-game action lists). make_evaluator(model, engine) -> engine evaluator (default: the model
+    called on the engine's input batch; e.g. nnfast.FusedNetworkEvaluator for a DualNetwork)."""
+    searches = [PvMcts(game_count, evaluate_count, device) for _ in range(2)]
+    if make_evaluator is None:
+        evaluators = (model_evaluator(model0, game_count, searches[0].engine),
+                      model_evaluator(model1, game_count, searches[1].engine))
+    else:
+        evaluators = (make_evaluator(model0, searches[0].engine), make_evaluator(model1, searches[1].engine))
+    return _play_games(searches, evaluators, (evaluate_count, evaluate_count), game_count, temperature, seed_base,
+                       batch_size, progress)
+
+
+def evaluate_vs_playouts(model, game_count=10, playouts=64, opponent_evaluate_count=1000, seed_base=0,
+                         temperature=0.0, evaluate_count=50, batch_size=8, device=None, make_evaluator=None,
+                         playout_seed=0, progress=None):
+    """The model's PV-MCTS player against plain MCTS over random playouts (the reference's commented-out
+    VS_MCTS opponent, evaluate_best_player.py:93-95 with game.py:294-379's mcts_action: there UCB1 over one
+    playout per evaluation, here the same search as the model's with PlayoutEvaluator in place of the network:
+    uniform priors, the mean of `playouts` playouts as the value, opponent_evaluate_count simulations per
+    move). All games run concurrently as in evaluate_network, on the Python-search semantics; the model moves
+    first in even games. Returns (the model's average point, per-game first-player points, per-game action
+    lists). make_evaluator(model, engine) -> the model's engine evaluator (default as evaluate_network)."""
+    searches = [PvMcts(game_count, evaluate_count, device), PvMcts(game_count, opponent_evaluate_count, device)]
+    if make_evaluator is None:
+        ev = model_evaluator(model, game_count, searches[0].engine)
+    else:
+        ev = make_evaluator(model, searches[0].engine)
+    evaluators = (ev, PlayoutEvaluator(searches[1].engine, playouts, playout_seed))
+    return _play_games(searches, evaluators, (evaluate_count, opponent_evaluate_count), game_count, temperature,
+                       seed_base, batch_size, progress)
 
 
 def first_player_value(state):
@@ -182,4 +211,4 @@ def self_play_py(model, game_count, seed_base=0, temperature=1.0, evaluate_count
 
 
 __all__ = ["ModelEvaluator", "first_player_value", "self_play_py", "PvMcts", "evaluate_network", "first_player_point", "model_evaluator",
-           "scores_from_visits"]
+           "scores_from_visits", "evaluate_vs_playouts"]

@@ -183,6 +183,23 @@ class Engine:
         check(self.lib.uttt_eval_hash_dev(self.h, ctypes.c_void_p(policy.data_ptr()),
                                           ctypes.c_void_p(value.data_ptr())))
 
+    def eval_playout_dev(self, policy, value, playouts, seed):
+        """The random-playout evaluator on the round's pending leaves (uttt_eval_playout_dev: states and count
+        on the device, after select or select_async): value = (wins - losses) / playouts, policy rows of ones."""
+        check(self.lib.uttt_eval_playout_dev(self.h, int(playouts), ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+                                             ctypes.c_void_p(policy.data_ptr()), ctypes.c_void_p(value.data_ptr())))
+
+    def playouts(self, states, playouts, seed=0):
+        """(wins, losses) int32 arrays of each state's side to move over `playouts` uniformly random games
+        (uttt_playouts; game.py:277-287 for many positions at once, terminal ones included)."""
+        st = as_states(states)
+        wins = np.zeros(len(st), np.int32)
+        losses = np.zeros(len(st), np.int32)
+        check(self.lib.uttt_playouts(self.h, st.ctypes.data_as(ctypes.POINTER(UtttState)), len(st), int(playouts),
+                                     ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), ptr(wins, ctypes.c_int32),
+                                     ptr(losses, ctypes.c_int32)))
+        return wins, losses
+
     def rounds_hash_async(self, ring_slot, policy, value, n_rounds):
         """n_rounds consecutive hash rounds in one call (uttt_rounds_hash_async): ring slots ring_slot ..
         ring_slot + n_rounds - 1 (mod 8), tags tag + 1 .. tag + n_rounds; returns the last round's tag."""

@@ -67,6 +67,33 @@ class HashEvaluator:
         return engine.rounds_hash_move(slot, self.policy, self.value, depth)
 
 
+class PlayoutEvaluator:
+    """Random-playout evaluator (game.py:277-287 as the leaf evaluation; no weights): value = mean result of
+    `playouts` uniformly random games from the leaf, uniform priors. Reads the pending leaves' states and the
+    count on the device (Engine.eval_playout_dev) after a blocking or an asynchronous select alike, and is a
+    function of the position and the seed alone: bit-reproducible and exact under the evaluation cache. It has
+    no one-call rounds, so SelfPlay runs it on the generic device-count path, one round in flight."""
+
+    needs_input = False
+    device_count = True
+
+    def __init__(self, engine, playouts=64, seed=0):
+        if not 1 <= int(playouts) <= 4096:
+            raise ValueError(f"playouts must be 1..4096 (got {playouts})")
+        self.engine = engine
+        self.playouts = int(playouts)
+        self.seed = int(seed)
+        dev = torch.device("cuda", engine.device)
+        self.policy = torch.zeros((engine.max_trees, 81), dtype=torch.float32, device=dev)
+        self.value = torch.zeros((engine.max_trees, 1), dtype=torch.float32, device=dev)
+
+    def __call__(self, x, n):
+        self.engine.eval_playout_dev(self.policy, self.value, self.playouts, self.seed)
+        if isinstance(n, RoundCount):
+            return self.policy, self.value
+        return self.policy[:n], self.value[:n]
+
+
 class NetworkEvaluator:
     """DualNetwork (or any model with its call signature) on the engine's device."""
 
@@ -588,5 +615,5 @@ def history_from_records(records):
     return hist
 
 
-__all__ = ["BatchedSearch", "SelfPlay", "HashEvaluator", "NetworkEvaluator", "history_from_records",
+__all__ = ["BatchedSearch", "SelfPlay", "HashEvaluator", "PlayoutEvaluator", "NetworkEvaluator", "history_from_records",
            "initial_states", "model_evaluator_factory", "default_lanes"]
