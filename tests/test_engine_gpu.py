@@ -396,6 +396,62 @@ def test_selfplay_other_temperatures_match_oracle(gpu, oracle_lib, tau):
         assert np.array_equal(r["values"], ref[g]["values"].astype(np.int64))
 
 
+def test_engine_lifecycle_regrows_and_destroys(gpu, oracle_lib):
+    """Create -> self-play -> self-play again with a larger record arena (the arena's regrowth) -> playouts of 1
+    and of 1,100 positions (past the playout buffers' first capacity of 1,024 rows) -> destroy, three times over
+    in one process. Every call returns UTTT_OK, both runs' records equal the oracle's, and the playout counts
+    equal uttt_playout_host's. (No assertion on free device memory: the machine's is not this process's alone;
+    that destroy frees every block is the sanitizer program's and the owner type's part.)"""
+    import ctypes
+    import torch
+    from uttt_amd._lib import UtttState
+    from uttt_amd.engine import Engine
+    n_games, seed, sims, batch = 4, 3131, 8, 2
+    ref = [oracle_lib.self_play_game_hash(seed + g, 1.0, sims, batch) for g in range(n_games)]
+
+    def play(e, ev, x, arena_plies):
+        e.selfplay_begin(0, n_games, seed, 1.0, sims, batch, arena_plies)
+        while e.move_begin() > 0:
+            while True:
+                n = e.select(x)
+                if n == 0:
+                    break
+                e.apply(*ev(x, n))
+            e.move_end()
+        ids, off, ln = e.games()
+        pl = e.plies(with_inputs=False)
+        assert ids.tolist() == list(range(n_games))
+        for g, o, n in zip(ids.tolist(), off.tolist(), ln.tolist()):
+            assert np.array_equal(pl["actions"][o:o + n].astype(np.int64), ref[g]["actions"].astype(np.int64)), g
+            assert np.array_equal(pl["policies"][o:o + n].view(np.uint64), ref[g]["policies"].view(np.uint64)), g
+            assert np.array_equal(pl["values"][o:o + n].astype(np.int64), ref[g]["values"].astype(np.int64)), g
+        return pl
+
+    def host_counts(lib, st, playouts, sd):
+        w, l = np.zeros(len(st), np.int32), np.zeros(len(st), np.int32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        assert lib.uttt_playout_host(st.ctypes.data_as(ctypes.POINTER(UtttState)), len(st), playouts, sd,
+                                     w.ctypes.data_as(i32), l.ctypes.data_as(i32)) == 0
+        return w, l
+
+    for _ in range(3):
+        e = Engine(4, 8)
+        ev = gpu.HashEvaluator(e)
+        x = torch.zeros((4, 3, 9, 9), dtype=torch.float32, device=torch.device("cuda", e.device))
+        first = play(e, ev, x, 4 * 81)
+        again = play(e, ev, x, 8 * 81)
+        for key in ("states", "policies", "actions", "values"):
+            assert first[key].tobytes() == again[key].tobytes(), key
+        st = np.resize(first["states"], 1100)  # the games' positions, repeated
+        for n in (1, 1100):
+            wins, losses = e.playouts(st[:n], 64, seed=9)
+            ends = np.ascontiguousarray(st[[0, n - 1]])
+            hw, hl = host_counts(e.lib, ends, 64, 9)
+            assert (wins[0], losses[0], wins[n - 1], losses[n - 1]) == (hw[0], hl[0], hw[1], hl[1]), n
+        assert e.lib.uttt_engine_destroy(e.h) == 0
+        e.h = None
+
+
 def test_play_uses_and_advances_global_numpy_rng(gpu):
     import self_play_cpp
     from oracle.hashnp import make_hash_model

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "engine_mem.h"
 #include "uttt_bits.h"
 #include "uttt_engine.h"
 #include "uttt_playout.h"
@@ -550,6 +551,30 @@ __device__ bool cache_insert(const EvalCache &c, const CacheProbe &pr, const utt
 // all-zero -> float64 uniform (kMetaP64); ONE child block (expand replaces, and
 // the k copies of a flush expand the same children); every node on the path
 // gets a network value, so its w becomes float32 (kMetaWF32).
+
+// A state's legal moves compacted over the wave: lane l holds action l (l0) and action 64 + l (l1, l < 17);
+// b0 / b1 their ballots, L = |legal|, i0 / i1 this lane's actions' ranks in action order. on == false
+// (k_begin's dead slots): no move counts as legal.
+struct Legal {
+    bool l0, l1;
+    uint64_t b0, b1;
+    int L, i0, i1;
+};
+__device__ __forceinline__ Legal legal_of(const uttt_state_t &s, bool on = true) {
+    const int lane = lane_id();
+    uint32_t m[3];
+    legal_mask(s, m);
+    Legal g;
+    g.l0 = on && bit_of(m, lane) != 0u;
+    g.l1 = on && lane < 17 && bit_of(m, 64 + lane) != 0u;
+    g.b0 = __ballot(g.l0);
+    g.b1 = __ballot(g.l1);
+    g.L = __popcll(g.b0) + __popcll(g.b1);
+    g.i0 = __popcll(g.b0 & lanes_below());
+    g.i1 = __popcll(g.b0) + __popcll(g.b1 & lanes_below());
+    return g;
+}
+
 __device__ float np_sum_f32_legal(float p0, float p1, uint64_t b0, uint64_t b1, int L) {
     // numpy pairwise_sum for float32, n <= 128: 8 strided accumulators, then the tail
     auto nth = [&](int idx) -> float {  // idx-th legal prior in action order (wave-uniform)
@@ -583,19 +608,21 @@ __device__ float np_sum_f32_legal(float p0, float p1, uint64_t b0, uint64_t b1, 
 // +0.0 to a sum that started at +0.0 changes nothing), then every lane reads the row back by
 // broadcast 16-byte reads and adds it up in order: one dependent add per prior, instead of a scalar
 // find-first-bit, a v_readlane and an add per prior.
-__device__ __forceinline__ float seq_sum_legal(float *row /* LDS, 16-B aligned, >= 84 floats */, float p0, float p1,
-                                               bool l0, bool l1, int i0, int i1, int L) {
+__device__ __forceinline__ void store_ranked_row(float *row /* LDS, 16-B aligned, >= 84 floats */, float p0, float p1,
+                                                 const Legal &g) {
     const int lane = lane_id();
-    if (l0) row[i0] = p0;
-    if (l1) row[i1] = p1;
-    const int L4 = (L + 3) & ~3;
-    if (lane >= L && lane < L4) row[lane] = 0.0f;  // L4 - L < 4 <= 64: lanes L .. L4-1 pad
+    if (g.l0) row[g.i0] = p0;
+    if (g.l1) row[g.i1] = p1;
+    // L4 - L < 4 <= 64: lanes L .. L4-1 pad (first item: no lane pads a row of 65-83 legal moves)
+    if (lane >= g.L && lane < ((g.L + 3) & ~3)) row[lane] = 0.0f;
+}
+__device__ __forceinline__ float sum_row4(const float *row, int L) {
     // the other lanes' stores before any lane's reads (LDS executes a wave's accesses in order; the
     // wait and the clobber keep the compiler from hoisting the reads above the stores)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     float sum = 0.0f;
     const float4 *r4 = reinterpret_cast<const float4 *>(row);
-    for (int i = 0; i < L4 / 4; ++i) {
+    for (int i = 0; i < ((L + 3) & ~3) / 4; ++i) {
         const float4 q = r4[i];
         sum += q.x;
         sum += q.y;
@@ -604,6 +631,10 @@ __device__ __forceinline__ float seq_sum_legal(float *row /* LDS, 16-B aligned, 
     }
     return sum;
 }
+__device__ __forceinline__ float seq_sum_legal(float *row, float p0, float p1, const Legal &g) {
+    store_ranked_row(row, p0, p1, g);
+    return sum_row4(row, g.L);
+}
 
 // rec_lo / rec_hi: this lane's path node's record (path[lane] / path[64 + lane]) as the select read it
 __device__ bool expand_backup(const Pool &pool, size_t base, int node, int depth, int path_lo, int path_hi,
@@ -611,17 +642,13 @@ __device__ bool expand_backup(const Pool &pool, size_t base, int node, int depth
                               int &node_count, bool py = false, float *row = nullptr, bool has_sum = false,
                               float known_sum = 0.0f, float *sum_out = nullptr, uint4 *root_out = nullptr) {
     const int lane = lane_id();
-    uint32_t m[3];
-    legal_mask(s, m);
-    const bool l0 = bit_of(m, lane) != 0u;
-    const bool l1 = lane < 17 && bit_of(m, 64 + lane) != 0u;
-    const uint64_t b0 = __ballot(l0), b1 = __ballot(l1);
-    const int L = __popcll(b0) + __popcll(b1);
+    const Legal g = legal_of(s);
+    const bool l0 = g.l0, l1 = g.l1;
+    const uint64_t b0 = g.b0, b1 = g.b1;
+    const int L = g.L, i0 = g.i0, i1 = g.i1;
     const int nb = node_count;
     const int blocks = py ? 1 : k;
     if ((int64_t)nb + (int64_t)blocks * L > pool.cap || L == 0) return false;
-    const int i0 = __popcll(b0 & lanes_below());
-    const int i1 = __popcll(b0) + __popcll(b1 & lanes_below());
     const float p0 = l0 ? raw0 : 0.0f;
     const float p1 = l1 ? raw1 : 0.0f;
     float sum = 0.0f;
@@ -630,7 +657,7 @@ __device__ bool expand_backup(const Pool &pool, size_t base, int node, int depth
     } else if (has_sum) {
         sum = known_sum;  // the cache record's (the same values added in the same order at insert)
     } else if (row) {
-        sum = seq_sum_legal(row, p0, p1, l0, l1, i0, i1, L);
+        sum = seq_sum_legal(row, p0, p1, g);
     } else {
         for (uint64_t bits = b0; bits; bits &= bits - 1ull) sum += readlane_f(p0, __builtin_ctzll(bits));
         for (uint64_t bits = b1; bits; bits &= bits - 1ull) sum += readlane_f(p1, __builtin_ctzll(bits));
@@ -685,6 +712,30 @@ __device__ bool expand_backup(const Pool &pool, size_t base, int node, int depth
 // after the previous move end's read of it) instead of by a memset on the stream, as is the search's
 // failure flag (Trees::count[3]);
 // search passes nullptr (all live) and packed states.
+
+// Tree t's root record, its uniform child block and its TreeCtl from the root state s (k_begin; k_search1 for
+// tree 0). py (pv_mcts.py:134): the root is a plain unexpanded node, evaluated by the first flush. on == false
+// (a self-play slot without a game): a root without children that is not live.
+__device__ __forceinline__ void init_root(const Pool &pool, const Trees &tr, int t, const uttt_state_t &s, bool on, int py) {
+    const int lane = lane_id();
+    const size_t base = (size_t)t * pool.cap;
+    const Legal g = legal_of(s, on || py);
+    const int L = py ? 0 : g.L;  // the child block's size
+    const float up = L ? 1.0f / (float)L : 0.0f;
+    if (!py && g.l0) pool.rec[base + 1 + g.i0] = new_child(up, (uint32_t)lane);
+    if (!py && g.l1) pool.rec[base + 1 + g.i1] = new_child(up, (uint32_t)(64 + lane));
+    if (lane == 0) {
+        pool.rec[base] = make_uint4(0u, 0u, make_meta(kNoAction, (uint32_t)L), make_link(L ? 1u : 0u, L ? 1u : 0u));
+        tr.root[t] = s;
+        TreeCtl c;
+        c.sims_done = 0;
+        c.node_count = 1 + L;
+        c.status = (on && g.L > 0) ? kLive : 0;
+        c.pad = 0;
+        tr.ctl[t] = c;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_begin(Pool pool, Trees tr, const char *src, int src_stride, const int32_t *live,
                                                   unsigned long long *err) {
     const int lane = lane_id();
@@ -697,40 +748,7 @@ __global__ __launch_bounds__(kBlock) void k_begin(Pool pool, Trees tr, const cha
     if (t >= tr.n_trees) return;
     const bool on = live ? (live[t] != 0) : true;
     const uttt_state_t s = *reinterpret_cast<const uttt_state_t *>(src + (size_t)t * src_stride);
-    const size_t base = (size_t)t * pool.cap;
-    uint32_t m[3];
-    legal_mask(s, m);
-    if (tr.py) {  // pv_mcts.py:134: the root is a plain unexpanded node (evaluated by the first flush)
-        const bool any = __ballot(bit_of(m, lane) != 0u) != 0ull || __ballot(lane < 17 && bit_of(m, 64 + lane) != 0u);
-        if (lane == 0) {
-            pool.rec[base] = make_uint4(0u, 0u, make_meta(kNoAction, 0u), 0u);
-            tr.root[t] = s;
-            TreeCtl c;
-            c.sims_done = 0;
-            c.node_count = 1;
-            c.status = (on && any) ? kLive : 0;
-            c.pad = 0;
-            tr.ctl[t] = c;
-        }
-        return;
-    }
-    const bool l0 = on && bit_of(m, lane);
-    const bool l1 = on && lane < 17 && bit_of(m, 64 + lane);
-    const uint64_t b0 = __ballot(l0), b1 = __ballot(l1);
-    const int L = __popcll(b0) + __popcll(b1);
-    const float up = L ? 1.0f / (float)L : 0.0f;
-    if (l0) pool.rec[base + 1 + __popcll(b0 & lanes_below())] = new_child(up, (uint32_t)lane);
-    if (l1) pool.rec[base + 1 + __popcll(b0) + __popcll(b1 & lanes_below())] = new_child(up, (uint32_t)(64 + lane));
-    if (lane == 0) {
-        pool.rec[base] = make_uint4(0u, 0u, make_meta(kNoAction, (uint32_t)L), make_link(L ? 1u : 0u, L ? 1u : 0u));
-        tr.root[t] = s;
-        TreeCtl c;
-        c.sims_done = 0;
-        c.node_count = 1 + L;
-        c.status = (on && L > 0) ? kLive : 0;
-        c.pad = 0;
-        tr.ctl[t] = c;
-    }
+    init_root(pool, tr, t, s, on, tr.py);
 }
 
 // --------------------------------------------------------------- select --
@@ -1351,6 +1369,16 @@ __global__ __launch_bounds__(256) void k_encode(Trees tr, float *__restrict__ x,
 // legal priors, sequential f32 sum in action order, divide (uniform 1/|legal|
 // if sum <= 0), append the child block, back up the value along the path.
 // per_copy: row rowbase[slot] + j holds copy j's result; else row = slot.
+
+// An apply that cannot go on: the tree's status gets the error bit (its ctl is stored as the wave holds it) and
+// the search's failure flag is raised; the host reports it at the move / search end
+__device__ __forceinline__ void stop_tree(const Trees &tr, int t, TreeCtl &ctl, int32_t err_bit) {
+    if (lane_id() != 0) return;
+    ctl.status |= err_bit;
+    tr.ctl[t] = ctl;
+    flag_tree_error(tr);
+}
+
 __device__ __forceinline__ void apply_wave(Pool pool, Trees tr, EvalCache cache, const float *__restrict__ policy,
                                            int64_t pld, const float *__restrict__ value, int64_t vld,
                                            const int32_t *__restrict__ rowbase, int per_copy,
@@ -1438,11 +1466,7 @@ __device__ __forceinline__ void apply_wave(Pool pool, Trees tr, EvalCache cache,
             const bool bad = (bit_of(m, lane) && !fin0) || (lane < 17 && bit_of(m, 64 + lane) && !fin1) ||
                              !__builtin_isfinite(v);
             if (__ballot(bad)) {
-                if (lane == 0) {
-                    ctl.status |= kErrNonFinite;
-                    tr.ctl[t] = ctl;
-                    flag_tree_error(tr);
-                }
+                stop_tree(tr, t, ctl, kErrNonFinite);
                 return;
             }
         }
@@ -1452,32 +1476,21 @@ __device__ __forceinline__ void apply_wave(Pool pool, Trees tr, EvalCache cache,
         float psum = 0.0f;
         if (!expand_backup(pool, base, r.node, depth, pn_lo, pn_hi, pr_lo, pr_hi, k, s, raw0, lane < 17 ? raw1 : 0.0f,
                            v, ctl.node_count, tr.py != 0, row, false, 0.0f, &psum)) {
-            if (lane == 0) {
-                ctl.status |= kErrCapacity;
-                tr.ctl[t] = ctl;
-                flag_tree_error(tr);
-            }
+            stop_tree(tr, t, ctl, kErrCapacity);
             return;
         }
         inserted = cacheable && cache_insert(cache, ipr, s, raw0, raw1, v, tr.py == 0, psum, defer);
         L = (ctl.node_count - nodes_before) / k;
     } else {
         // the reference's exact call pattern: k results, one per queued copy, applied in order
-        uint32_t m[3];
-        legal_mask(s, m);
-        const bool l0 = bit_of(m, lane) != 0u;
-        const bool l1 = lane < 17 && bit_of(m, 64 + lane) != 0u;
-        const uint64_t b0 = __ballot(l0), b1 = __ballot(l1);
-        L = __popcll(b0) + __popcll(b1);
-        const int i0 = __popcll(b0 & lanes_below());
-        const int i1 = __popcll(b0) + __popcll(b1 & lanes_below());
+        const Legal g = legal_of(s);
+        const bool l0 = g.l0, l1 = g.l1;
+        const uint64_t b0 = g.b0, b1 = g.b1;
+        const int i0 = g.i0, i1 = g.i1;
+        L = g.L;
         const int nb = ctl.node_count;
         if ((int64_t)nb + (int64_t)k * L > pool.cap || L == 0) {
-            if (lane == 0) {
-                ctl.status |= kErrCapacity;
-                tr.ctl[t] = ctl;
-                flag_tree_error(tr);
-            }
+            stop_tree(tr, t, ctl, kErrCapacity);
             return;
         }
         // the copies' rows in chunks of kCopyChunk whose loads are all issued before the first use: one
@@ -1514,27 +1527,11 @@ __device__ __forceinline__ void apply_wave(Pool pool, Trees tr, EvalCache cache,
         };
         // copy_rows: lane jj's sum of the chunk's copy jj, its legal priors compacted in action order into an
         // LDS row (seq_sum_legal's order and zero padding, so the same f32 sum as the one-lane loop below)
-        const int L4 = (L + 3) & ~3;
         float csum = 0.0f;
         auto chunk_sums = [&]() {
 #pragma unroll
-            for (int jj = 0; jj < kCopyChunk; ++jj) {
-                float *rw = copy_rows + jj * 84;
-                if (l0) rw[i0] = c0[jj];
-                if (l1) rw[i1] = c1[jj];
-                if (lane >= L && lane < L4) rw[lane] = 0.0f;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's stores before any lane's reads
-            const float4 *r4 = reinterpret_cast<const float4 *>(copy_rows + (lane & (kCopyChunk - 1)) * 84);
-            float acc = 0.0f;
-            for (int i = 0; i < L4 / 4; ++i) {
-                const float4 q = r4[i];
-                acc += q.x;
-                acc += q.y;
-                acc += q.z;
-                acc += q.w;
-            }
-            csum = acc;
+            for (int jj = 0; jj < kCopyChunk; ++jj) store_ranked_row(copy_rows + jj * 84, c0[jj], c1[jj], g);
+            csum = sum_row4(copy_rows + (lane & (kCopyChunk - 1)) * 84, L);
         };
         bool bad = false;  // any copy's legal prior or value non-finite: nothing is applied (as above)
         for (int j0 = 0; j0 < k; j0 += kCopyChunk) {
@@ -1544,11 +1541,7 @@ __device__ __forceinline__ void apply_wave(Pool pool, Trees tr, EvalCache cache,
                 bad |= !__builtin_isfinite(c0[jj]) || !__builtin_isfinite(c1[jj]) || !__builtin_isfinite(cv[jj]);
         }
         if (__ballot(bad)) {
-            if (lane == 0) {
-                ctl.status |= kErrNonFinite;
-                tr.ctl[t] = ctl;
-                flag_tree_error(tr);
-            }
+            stop_tree(tr, t, ctl, kErrNonFinite);
             return;
         }
         uint4 r_lo = pr_lo, r_hi = pr_hi;
@@ -1641,12 +1634,9 @@ __global__ __launch_bounds__(kWave) void k_flush1(Pool pool, Trees tr, EvalCache
 
 // The hash evaluator's outputs for one state into row `row` (k_hash_leaves' and k_round1's): bit j = ch * 81 +
 // R * 9 + C of the network input, as k_encode writes it, so the words and outputs are k_hash_eval's.
-__device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__restrict__ policy, float *__restrict__ value,
-                                              int row) {
+// The network input of state s (m: its legal mask) as four ballot words over its 243 bits
+__device__ __forceinline__ void input_words(const uttt_state_t &s, const uint32_t (&m)[3], uint64_t (&w)[4]) {
     const int lane = lane_id();
-    uint32_t m[3];
-    legal_mask(s, m);
-    uint64_t w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int j = i * 64 + lane;
@@ -1657,6 +1647,14 @@ __device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__re
         }
         w[i] = __ballot(on);
     }
+}
+__device__ __forceinline__ void hash_leaf_row(const uttt_state_t &s, float *__restrict__ policy, float *__restrict__ value,
+                                              int row) {
+    const int lane = lane_id();
+    uint32_t m[3];
+    legal_mask(s, m);
+    uint64_t w[4];
+    input_words(s, m, w);
     const uint64_t h = hash_words(w);
     policy[(size_t)row * 81 + lane] = hash_prior(h, lane);
     if (lane < 17) policy[(size_t)row * 81 + 64 + lane] = hash_prior(h, 64 + lane);
@@ -1945,17 +1943,8 @@ __device__ __forceinline__ void playout_wave(const uttt_state_t &s, int P, uint6
     const int lane = lane_id();
     uint32_t m[3];
     legal_mask(s, m);
-    uint64_t w[4];  // the input words as hash_leaf_row forms them
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j = i * 64 + lane;
-        bool on = false;
-        if (j < 243) {
-            const int ch = j / 81, a = action_at(j % 81);
-            on = (ch == 0 ? bit_of(s.own, a) : (ch == 1 ? bit_of(s.opp, a) : bit_of(m, a))) != 0u;
-        }
-        w[i] = __ballot(on);
-    }
+    uint64_t w[4];
+    input_words(s, m, w);
     const uint64_t h = playout_key(w, seed);
     wins = losses = 0;
     for (int base = 0; base < P; base += kWave) {
@@ -2059,40 +2048,8 @@ __global__ __launch_bounds__(kWave) void k_search1(Pool pool, Trees tr, EvalCach
     __shared__ __attribute__((aligned(16))) float s_copies[8 * 84];  // per-copy rows' prior sums (apply_wave)
     const int lane = lane_id();
     if (lane == 0) s_rowbase = 0;
-    if (!resume) {  // k_begin's body for tree 0 (root expanded with uniform priors; py semantics: plain root)
-        uint32_t m[3];
-        legal_mask(root, m);
-        if (tr.py) {
-            const bool any = __ballot(bit_of(m, lane) != 0u) != 0ull || __ballot(lane < 17 && bit_of(m, 64 + lane) != 0u);
-            if (lane == 0) {
-                pool.rec[0] = make_uint4(0u, 0u, make_meta(kNoAction, 0u), 0u);
-                tr.root[0] = root;
-                TreeCtl c;
-                c.sims_done = 0;
-                c.node_count = 1;
-                c.status = any ? kLive : 0;
-                c.pad = 0;
-                tr.ctl[0] = c;
-            }
-        } else {
-            const bool l0 = bit_of(m, lane) != 0u;
-            const bool l1 = lane < 17 && bit_of(m, 64 + lane) != 0u;
-            const uint64_t b0 = __ballot(l0), b1 = __ballot(l1);
-            const int L = __popcll(b0) + __popcll(b1);
-            const float up = L ? 1.0f / (float)L : 0.0f;
-            if (l0) pool.rec[1 + __popcll(b0 & lanes_below())] = new_child(up, (uint32_t)lane);
-            if (l1) pool.rec[1 + __popcll(b0) + __popcll(b1 & lanes_below())] = new_child(up, (uint32_t)(64 + lane));
-            if (lane == 0) {
-                pool.rec[0] = make_uint4(0u, 0u, make_meta(kNoAction, (uint32_t)L), make_link(L ? 1u : 0u, L ? 1u : 0u));
-                tr.root[0] = root;
-                TreeCtl c;
-                c.sims_done = 0;
-                c.node_count = 1 + L;
-                c.status = L > 0 ? kLive : 0;
-                c.pad = 0;
-                tr.ctl[0] = c;
-            }
-        }
+    if (!resume) {  // as k_begin for tree 0
+        init_root(pool, tr, 0, root, true, tr.py);
         wave_memory_fence();
     }
     bool apply = resume != 0;  // resume: the command of sequence `seq` is waiting in host memory
@@ -2714,6 +2671,32 @@ __global__ void k_hwc(const uttt_state_t *st, int64_t n, float *out) {
 // ============================================================== host side ==
 using namespace uttt;
 
+// The allocate / free pairs behind the engine's buffers (engine_mem.h). Every block the engine owns is a
+// DevBuf or a PinBuf member of uttt_engine: `delete e` frees them all, a failed growth leaves an empty buffer.
+struct DevMem {
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        const hipError_t r = hipMalloc(&p, bytes ? bytes : 16);
+        if (r != hipSuccess) set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(r));
+        return r == hipSuccess ? p : nullptr;
+    }
+    static void free(void *p) { (void)hipFree(p); }
+};
+template <unsigned Flags>
+struct PinMem {
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        if (hipHostMalloc(&p, bytes, Flags) == hipSuccess) return p;
+        set_error("hipHostMalloc failed");
+        return nullptr;
+    }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <typename T>
+using DevBuf = Buf<T, DevMem>;
+template <typename T>
+using PinBuf = Buf<T, PinMem<hipHostMallocCoherent>>;  // fine-grained: the device's system-scope stores land at once
+
 struct uttt_engine {
     int device = 0;
     int max_trees = 0;
@@ -2721,13 +2704,19 @@ struct uttt_engine {
     int64_t cap = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    // what the kernels take by value: raw pointers, filled from the owners below (alloc_n)
     Pool pool{};
     Trees tr{};
-    int32_t *h_count = nullptr;  // pinned
-    int32_t *h_ring = nullptr;   // fine-grained pinned: kCountRing x {pending, stopped, left, tag}, k_scan-written
-    HostLeaf *h_leaf = nullptr;  // fine-grained pinned: a one-tree round's result (uttt_search_select_host)
-    float *h_eval = nullptr;     // fine-grained pinned: its evaluation, read by k_apply (uttt_search_apply_host):
-                                 // [rows][96] policy, [rows] value, one int32 0 (the per-copy row base)
+    DevBuf<uint4> m_rec, m_path_rec;
+    DevBuf<TreeCtl> m_ctl;
+    DevBuf<uttt_state_t> m_root, m_leaf;
+    DevBuf<LeafRec> m_leafrec;
+    DevBuf<int32_t> m_path, m_pending, m_tree_of, m_depth_of, m_count;
+    Buf<int32_t, PinMem<hipHostMallocDefault>> h_count;  // pinned
+    PinBuf<int32_t> h_ring;   // kCountRing x {pending, stopped, left, tag}, k_scan-written
+    PinBuf<HostLeaf> h_leaf;  // a one-tree round's result (uttt_search_select_host)
+    PinBuf<float> h_eval;     // its evaluation, read by k_apply (uttt_search_apply_host):
+                              // [rows][96] policy, [rows] value, one int32 0 (the per-copy row base)
     int64_t h_eval_rows = 0;
     // a hash round's evaluation staged by uttt_round_hash_async (rows by tree), applied by the next round's
     // k_round1 (or by flush_dev_apply before any other call that reads the trees); UTTT_FUSED_ROUNDS=0: separate
@@ -2735,30 +2724,34 @@ struct uttt_engine {
     const float *dev_apply_policy = nullptr, *dev_apply_value = nullptr;
     bool dev_apply_staged = false;
     // the resident one-tree search (uttt_search1_*, k_search1): its host block and evaluation rows
-    Search1Host *h_s1 = nullptr;  // fine-grained pinned: Search1Host, then policy [cap][96], value [cap]
-    int32_t s1_cap = 0, s1_seq = 0;
+    PinBuf<char> s1_mem;          // Search1Host, then policy [cap][96], value [cap]
+    Search1Host *h_s1 = nullptr;  // s1_mem's head
+    int64_t s1_cap = 0;
+    int32_t s1_seq = 0;
     bool s1_alive = false;  // a k_search1 wave may still be resident on the stream
     uttt_state_t s1_root{};
     float s1_temperature = 0.0f;
-    uint32_t *d_r1ctl = nullptr;     // k_round1's arrival counters and per-block partials (zero between rounds)
-    // uttt_rounds_hash_move's per-block count words: host [kCountRing][part_cap] (fine-grained pinned), device
-    // [2][part_cap] (the previous round's, for the empty-round check)
-    uint32_t *h_part = nullptr, *d_part = nullptr;
+    DevBuf<uint32_t> d_r1ctl;     // k_round1's arrival counters and per-block partials (zero between rounds)
+    // uttt_rounds_hash_move's per-block count words: host [kCountRing][part_cap], device [2][part_cap] (the
+    // previous round's, for the empty-round check)
+    PinBuf<uint32_t> h_part;
+    DevBuf<uint32_t> d_part;
     int32_t part_cap = 0;
     uint32_t round_parity = 0;  // the per-block rounds' select-statistics parity (alternates every round)
     int32_t host_apply_rows = 0;  // a one-tree evaluation staged by uttt_search_apply_host, applied by the next
                                   // k_flush1 (or by flush_host_apply before any other call that reads the tree)
     int32_t leaf_tag = 0;
-    int32_t *d_rowbase = nullptr;
-    float *d_pol_scratch = nullptr;
-    float *d_val_scratch = nullptr;
+    DevBuf<int32_t> d_rowbase;  // with the two scratch buffers one group (ensure_scratch)
+    DevBuf<float> d_pol_scratch, d_val_scratch;
     int64_t scratch_rows = 0;
-    uttt_state_t *d_po_states = nullptr;  // uttt_playouts: the positions and their [wins | losses], grown on demand
-    int32_t *d_po_counts = nullptr;
+    DevBuf<uttt_state_t> d_po_states;  // uttt_playouts: the positions and their [wins | losses], one group
+    DevBuf<int32_t> d_po_counts;
     int64_t po_rows = 0;
-    float *d_scores = nullptr;
-    int32_t *d_nlegal = nullptr;
-    int32_t *d_visits = nullptr;
+    DevBuf<float> d_scores;
+    DevBuf<int32_t> d_nlegal, d_visits;
+    // uttt_engine_device_bytes: what alloc_n allocated plus the engine's own cache table, as before the buffers
+    // had owners; the blocks grown on demand (scratch, playouts, arena, game table) and pinned memory are not
+    // counted (counting them would change what callers see)
     int64_t bytes = 0;
     // round state
     int phase = 0;  // 0 idle, 1 search begun (select next), 2 selected (apply next),
@@ -2766,20 +2759,31 @@ struct uttt_engine {
     int n_pending = 0;
     bool selfplay = false;
     // self-play
-    SelfPlay sp{};
+    SelfPlay sp{};  // raw pointers, filled from these owners; the arena's four grow as one group (sp.arena_cap)
+    DevBuf<Slot> m_slot;
+    DevBuf<uint32_t> m_mt_key;
+    DevBuf<int32_t> m_mt_pos, m_live, m_work;
+    DevBuf<uttt_state_t> m_ply_state, m_ar_state;
+    DevBuf<double> m_ply_policy, m_ar_policy;
+    DevBuf<int8_t> m_ply_action, m_ar_action, m_ar_value;
+    DevBuf<GameEntry> m_games;
+    DevBuf<int64_t> m_ctr;
     int64_t sp_arena_used = 0;
-    int64_t *h_move = nullptr;          // pinned: [0..3] sp.ctr after the last move end, [4] error word
-    unsigned long long *d_err = nullptr;  // first failed tree of a move: (tree << 32) | status, or ~0
-    // evaluation cache (off unless uttt_engine_set_cache)
+    PinBuf<int64_t> h_move;             // [0..3] sp.ctr after the last move end, [4] error word
+    DevBuf<unsigned long long> d_err;   // first failed tree of a move: (tree << 32) | status, or ~0
+    // evaluation cache (off unless uttt_engine_set_cache): `cache` is the view the kernels take; the table
+    // is this engine's (m_cache_*) or, after uttt_engine_share_cache, another engine's (nothing owned here)
     EvalCache cache{};
+    DevBuf<uint32_t> m_cache_flag;
+    DevBuf<char> m_cache_rec;
     int cache_log2 = 0;
     int cache_clear_every = 0;
     bool cache_owner = true;  // false: the table belongs to another engine (uttt_engine_share_cache)
     int64_t moves = 0;
-    unsigned long long *d_cache_ctr = nullptr;
+    DevBuf<unsigned long long> d_cache_ctr;
     // telemetry
     bool timing = false;
-    unsigned long long *d_bytes = nullptr;  // [kKernelCount]
+    DevBuf<unsigned long long> d_bytes;  // [kKernelCount]
     struct Ev {
         int kid;
         hipEvent_t a, b;
@@ -2788,26 +2792,17 @@ struct uttt_engine {
     std::vector<hipEvent_t> ev_pool;
     double ms[kKernelCount] = {};
     int64_t launches[kKernelCount] = {};
-    std::vector<void *> allocs;
 };
 
 namespace {
 
-int dev_alloc(uttt_engine *e, void **p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t r = hipMalloc(p, bytes);
-    if (r != hipSuccess) {
-        set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(r));
-        return UTTT_ERR_HIP;
-    }
-    e->allocs.push_back(*p);
-    e->bytes += (int64_t)bytes;
-    return UTTT_OK;
-}
-
+// n elements in owner b, counted in uttt_engine_device_bytes; view (optional): the kernels' raw pointer to it
 template <typename T>
-int alloc_n(uttt_engine *e, T **p, size_t n) {
-    return dev_alloc(e, reinterpret_cast<void **>(p), n * sizeof(T));
+int alloc_n(uttt_engine *e, DevBuf<T> &b, size_t n, T **view = nullptr) {
+    if (int rc = b.grow((int64_t)n)) return rc;
+    if (view) *view = b;
+    e->bytes += (int64_t)(n ? n * sizeof(T) : 16);
+    return UTTT_OK;
 }
 
 hipEvent_t get_event(uttt_engine *e) {
@@ -2882,6 +2877,7 @@ void drain_events(uttt_engine *e) {
     e->pending_ev.resize(keep);
 }
 
+unsigned long long *stats_ptr(uttt_engine *e) { return e->timing ? e->d_bytes.get() : nullptr; }
 unsigned long long *bytes_ptr(uttt_engine *e, int kid) { return e->timing ? e->d_bytes + (size_t)kid * kRow : nullptr; }
 
 int check_launch() {
@@ -2899,16 +2895,42 @@ int ensure_scratch(uttt_engine *e, int64_t rows) {
     if (rows <= e->scratch_rows) return UTTT_OK;
     int64_t n = e->scratch_rows ? e->scratch_rows : 1024;
     while (n < rows) n *= 2;
-    if (e->d_pol_scratch) {
-        (void)hipFree(e->d_pol_scratch);
-        (void)hipFree(e->d_val_scratch);
-        (void)hipFree(e->d_rowbase);
+    return grow_group(e->scratch_rows, n, e->d_pol_scratch, n * 81, e->d_val_scratch, n, e->d_rowbase,
+                      std::max<int64_t>(n, e->max_trees));
+}
+
+// Wait for words the device stores into fine-grained host memory: spin until ready(), no stream sync. The
+// failure checks run only for a wait past 20 ms, then every 1,024 polls: a stream query goes through the
+// runtime's locks and cost tree-only self-play 7% when made every ~40 us while the rounds ran (round 6). A
+// failed stream is an error; on_drained() answers a stream that finished without the words (an error code, or
+// UTTT_OK after relaunching what stores them); `what` names the result in the 60 s timeout's message.
+template <typename Ready, typename Drained>
+int spin_wait(uttt_engine *e, const char *what, Ready &&ready, Drained &&on_drained) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned it = 1; !ready(); ++it) {
+        if ((it & 1023u) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
+            const hipError_t q = hipStreamQuery(e->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) {
+                set_error("engine stream failed: %s", hipGetErrorString(q));
+                return UTTT_ERR_HIP;
+            }
+            if (q == hipSuccess && !ready())
+                if (int rc = on_drained()) return rc;
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
+                set_error("engine: %s not stored within 60 s", what);
+                return UTTT_ERR_HIP;
+            }
+        }
+        __builtin_ia32_pause();
     }
-    HIP_TRY(hipMalloc((void **)&e->d_pol_scratch, (size_t)n * 81 * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&e->d_val_scratch, (size_t)n * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&e->d_rowbase, (size_t)std::max<int64_t>(n, e->max_trees) * sizeof(int32_t)));
-    e->scratch_rows = n;
     return UTTT_OK;
+}
+// on_drained for a wait nothing can restart: the error `text`
+auto drained_error(const char *text) {
+    return [text] {
+        set_error("%s", text);
+        return UTTT_ERR_HIP;
+    };
 }
 
 }  // namespace
@@ -2976,37 +2998,25 @@ int uttt_engine_create(int32_t device, int32_t max_trees, int32_t max_sims, uttt
     e->stream = e->own_stream;
     const size_t nodes = (size_t)max_trees * (size_t)e->cap;
     e->pool.cap = e->cap;
-    if ((rc = alloc_n(e, &e->pool.rec, nodes))) return fail(rc);
-    if ((rc = alloc_n(e, &e->tr.ctl, max_trees)) || (rc = alloc_n(e, &e->tr.root, max_trees)) ||
-        (rc = alloc_n(e, &e->tr.leaf, max_trees)) || (rc = alloc_n(e, &e->tr.rec, max_trees)) ||
-        (rc = alloc_n(e, &e->tr.path, (size_t)max_trees * kMaxDepth)) ||
-        (rc = alloc_n(e, &e->tr.path_rec, (size_t)max_trees * kMaxDepth)) || (rc = alloc_n(e, &e->tr.pending, max_trees)) ||
-        (rc = alloc_n(e, &e->tr.tree_of, max_trees)) || (rc = alloc_n(e, &e->tr.depth_of, max_trees)) ||
-        (rc = alloc_n(e, &e->tr.count, 4)) ||
-        (rc = alloc_n(e, &e->d_scores, (size_t)max_trees * 81)) || (rc = alloc_n(e, &e->d_visits, (size_t)max_trees * 81)) ||
-        (rc = alloc_n(e, &e->d_nlegal, max_trees)) || (rc = alloc_n(e, &e->d_bytes, kKernelCount * kRow)) ||
-        (rc = alloc_n(e, &e->d_cache_ctr, 4 * kRow)) ||
-        (rc = alloc_n(e, &e->d_r1ctl, (size_t)kR1Partial + (size_t)grid_waves(max_trees))))
+    if ((rc = alloc_n(e, e->m_rec, nodes, &e->pool.rec))) return fail(rc);
+    if ((rc = alloc_n(e, e->m_ctl, max_trees, &e->tr.ctl)) || (rc = alloc_n(e, e->m_root, max_trees, &e->tr.root)) ||
+        (rc = alloc_n(e, e->m_leaf, max_trees, &e->tr.leaf)) || (rc = alloc_n(e, e->m_leafrec, max_trees, &e->tr.rec)) ||
+        (rc = alloc_n(e, e->m_path, (size_t)max_trees * kMaxDepth, &e->tr.path)) ||
+        (rc = alloc_n(e, e->m_path_rec, (size_t)max_trees * kMaxDepth, &e->tr.path_rec)) ||
+        (rc = alloc_n(e, e->m_pending, max_trees, &e->tr.pending)) ||
+        (rc = alloc_n(e, e->m_tree_of, max_trees, &e->tr.tree_of)) ||
+        (rc = alloc_n(e, e->m_depth_of, max_trees, &e->tr.depth_of)) || (rc = alloc_n(e, e->m_count, 4, &e->tr.count)) ||
+        (rc = alloc_n(e, e->d_scores, (size_t)max_trees * 81)) || (rc = alloc_n(e, e->d_visits, (size_t)max_trees * 81)) ||
+        (rc = alloc_n(e, e->d_nlegal, max_trees)) || (rc = alloc_n(e, e->d_bytes, kKernelCount * kRow)) ||
+        (rc = alloc_n(e, e->d_cache_ctr, 4 * kRow)) ||
+        (rc = alloc_n(e, e->d_r1ctl, (size_t)kR1Partial + (size_t)grid_waves(max_trees))) ||
+        (rc = alloc_n(e, e->d_err, 1)))
         return fail(rc);
-    if ((rc = alloc_n(e, &e->d_err, 1))) return fail(rc);
-    if (hipHostMalloc((void **)&e->h_move, sizeof(int64_t) * 5, hipHostMallocCoherent) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return fail(UTTT_ERR_HIP);
-    }
-    if (hipHostMalloc((void **)&e->h_ring, sizeof(int32_t) * 4 * kCountRing, hipHostMallocCoherent) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return fail(UTTT_ERR_HIP);
-    }
+    if ((rc = e->h_move.grow(5)) || (rc = e->h_ring.grow(4 * kCountRing)) || (rc = e->h_leaf.grow(1)) ||
+        (rc = e->h_count.grow(4)))
+        return fail(rc);
     memset(e->h_ring, 0, sizeof(int32_t) * 4 * kCountRing);
-    if (hipHostMalloc((void **)&e->h_leaf, sizeof(HostLeaf), hipHostMallocCoherent) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return fail(UTTT_ERR_HIP);
-    }
     memset(e->h_leaf, 0, sizeof(HostLeaf));
-    if (hipHostMalloc((void **)&e->h_count, sizeof(int32_t) * 4, hipHostMallocDefault) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return fail(UTTT_ERR_HIP);
-    }
     if (hipMemsetAsync(e->tr.ctl, 0, sizeof(TreeCtl) * max_trees, e->stream) != hipSuccess ||
         hipMemsetAsync(e->d_bytes, 0, sizeof(unsigned long long) * kKernelCount * kRow, e->stream) != hipSuccess ||
         hipMemsetAsync(e->d_cache_ctr, 0, sizeof(unsigned long long) * 4 * kRow, e->stream) != hipSuccess ||
@@ -3029,25 +3039,8 @@ int uttt_engine_destroy(uttt_engine_t *e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     drain_events(e);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
-    for (void *p : e->allocs) (void)hipFree(p);
-    if (e->d_pol_scratch) (void)hipFree(e->d_pol_scratch);
-    if (e->d_val_scratch) (void)hipFree(e->d_val_scratch);
-    if (e->d_rowbase) (void)hipFree(e->d_rowbase);
-    if (e->d_po_states) (void)hipFree(e->d_po_states);
-    if (e->d_po_counts) (void)hipFree(e->d_po_counts);
-    if (e->cache_owner) {
-        if (e->cache.flag) (void)hipFree(e->cache.flag);
-        if (e->cache.rec) (void)hipFree(e->cache.rec);
-    }
-    if (e->h_count) (void)hipHostFree(e->h_count);
-    if (e->h_ring) (void)hipHostFree(e->h_ring);
-    if (e->h_part) (void)hipHostFree(e->h_part);
-    if (e->h_leaf) (void)hipHostFree(e->h_leaf);
-    if (e->h_eval) (void)hipHostFree(e->h_eval);
-    if (e->h_s1) (void)hipHostFree(e->h_s1);
-    if (e->h_move) (void)hipHostFree(e->h_move);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
-    delete e;
+    delete e;  // every device and pinned block: the members' destructors (engine_mem.h)
     return UTTT_OK;
 }
 
@@ -3095,23 +3088,28 @@ static int search_begin_common(uttt_engine *e, int32_t n_trees, int32_t sims, in
     return UTTT_OK;
 }
 
+// The start of a search with given semantics (fn: the caller's name for the message): the argument check, then
+// search_begin_common
+static int begin_with_semantics(uttt_engine *e, const char *fn, const uttt_state_t *roots, int32_t n_trees, int32_t sims,
+                                int32_t batch, int32_t semantics) {
+    if (!e || !roots || (semantics != UTTT_SEMANTICS_CPP && semantics != UTTT_SEMANTICS_PY)) {
+        set_error("%s: bad arguments (semantics 0 = cpp, 1 = py)", fn);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = search_begin_common(e, n_trees, sims, batch)) return rc;
+    e->tr.py = semantics == UTTT_SEMANTICS_PY ? 1 : 0;
+    e->selfplay = false;
+    return UTTT_OK;
+}
+
 int uttt_search_begin(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch) {
     return uttt_search_begin_mode(e, roots, n_trees, sims, batch, UTTT_SEMANTICS_CPP);
 }
 
 int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch,
                            int32_t semantics) {
-    if (!e || !roots || (semantics != UTTT_SEMANTICS_CPP && semantics != UTTT_SEMANTICS_PY)) {
-        set_error("uttt_search_begin_mode: bad arguments (semantics 0 = cpp, 1 = py)");
-        return UTTT_ERR_ARG;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    e->host_apply_rows = 0;  // a staged evaluation of the previous search is dropped with it
-    e->dev_apply_staged = false;
-    int rc = search_begin_common(e, n_trees, sims, batch);
-    if (rc) return rc;
-    e->tr.py = semantics == UTTT_SEMANTICS_PY ? 1 : 0;
-    e->selfplay = false;
+    if (int rc = begin_with_semantics(e, "uttt_search_begin_mode", roots, n_trees, sims, batch, semantics)) return rc;
     HIP_TRY(hipMemcpyAsync(e->tr.leaf, roots, sizeof(uttt_state_t) * n_trees, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_begin, dim3(grid_waves(n_trees)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
                        (const char *)e->tr.leaf, (int)sizeof(uttt_state_t), (const int32_t *)nullptr,
@@ -3120,6 +3118,16 @@ int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t 
 }
 
 static int flush_host_apply(uttt_engine *e);
+
+// One descent of every tree and the scan of its pending leaves (host_count, optional: a count-ring slot the
+// scan also stores the counts and then `tag` into)
+static int launch_select_scan(uttt_engine *e, int32_t *host_count, int32_t tag) {
+    timed_launch(e, kKSelect, e->tr.py ? k_select<true> : k_select<false>, dim3(grid_waves(e->tr.n_trees)),
+                 dim3(kBlock), e->pool, e->tr, e->cache, stats_ptr(e));
+    if (int rc = check_launch()) return rc;
+    timed_launch(e, kKScan, k_scan, dim3(1), dim3(1024), e->tr, stats_ptr(e), host_count, tag);
+    return check_launch();
+}
 
 int uttt_search_select(uttt_engine_t *e, float *nn_input, int32_t *n_pending) {
     if (!e || !n_pending) return UTTT_ERR_ARG;
@@ -3134,12 +3142,7 @@ int uttt_search_select(uttt_engine_t *e, float *nn_input, int32_t *n_pending) {
     // leaf but some were stopped, select again (every launch completes >= 1 simulation
     // of each stopped tree, so this ends)
     for (;;) {
-        timed_launch(e, kKSelect, e->tr.py ? k_select<true> : k_select<false>, dim3(grid_waves(e->tr.n_trees)),
-                     dim3(kBlock), e->pool, e->tr, e->cache, e->timing ? e->d_bytes : nullptr);
-        if ((rc = check_launch())) return rc;
-        timed_launch(e, kKScan, k_scan, dim3(1), dim3(1024), e->tr, e->timing ? e->d_bytes : nullptr,
-                     (int32_t *)nullptr, (int32_t)0);
-        if ((rc = check_launch())) return rc;
+        if ((rc = launch_select_scan(e, nullptr, 0))) return rc;
         HIP_TRY(hipMemcpyAsync(e->h_count, e->tr.count, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         drain_events(e);
@@ -3183,12 +3186,7 @@ static int select_async_impl(uttt_engine_t *e, int32_t *host_count, int32_t tag)
     }
     HIP_TRY(hipSetDevice(e->device));
     if (int rc0 = flush_host_apply(e)) return rc0;
-    int rc = 0;
-    timed_launch(e, kKSelect, e->tr.py ? k_select<true> : k_select<false>, dim3(grid_waves(e->tr.n_trees)),
-                 dim3(kBlock), e->pool, e->tr, e->cache, e->timing ? e->d_bytes : nullptr);
-    if ((rc = check_launch())) return rc;
-    timed_launch(e, kKScan, k_scan, dim3(1), dim3(1024), e->tr, e->timing ? e->d_bytes : nullptr, host_count, tag);
-    if ((rc = check_launch())) return rc;
+    if (int rc = launch_select_scan(e, host_count, tag)) return rc;
     e->n_pending = -1;
     e->phase = 3;
     return UTTT_OK;
@@ -3230,28 +3228,16 @@ int uttt_search_pending(uttt_engine_t *e, uttt_state_t *states, int32_t *copies)
     return UTTT_OK;
 }
 
-// Wait for a tag the device stores into fine-grained host memory (k_scan): spin, no stream sync.
-static int wait_host_tag(uttt_engine *e, const int32_t *tag_word, int32_t tag) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 1;; ++it) {
-        if (__atomic_load_n(tag_word, __ATOMIC_ACQUIRE) == tag) return UTTT_OK;
-        if ((it & 1023u) == 0u) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-                set_error("engine stream failed: %s", hipGetErrorString(q));
-                return UTTT_ERR_HIP;
-            }
-            if (q == hipSuccess && __atomic_load_n(tag_word, __ATOMIC_ACQUIRE) != tag) {
-                set_error("engine: the stream drained without storing the round's tag");
-                return UTTT_ERR_HIP;
-            }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-                set_error("engine: round result not stored within 60 s");
-                return UTTT_ERR_HIP;
-            }
-        }
-        __builtin_ia32_pause();
+// Evaluation rows into a pinned block a kernel reads (policy rows at a 96-float stride, 81 used), complete
+// before whatever the caller does next to make the device read them (x86 keeps the stores in order; the fence
+// keeps the compiler's)
+static void stage_rows(float *dst_policy, float *dst_value, const float *policy, int64_t pld, const float *value,
+                       int32_t rows) {
+    for (int32_t r = 0; r < rows; ++r) {
+        memcpy(dst_policy + (size_t)r * 96, policy + (size_t)r * pld, 81 * sizeof(float));
+        dst_value[r] = value[r];
     }
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
 }
 
 // The staged evaluation's k_apply arguments (pinned host memory; rows 1: one row for the leaf's k copies,
@@ -3315,28 +3301,15 @@ static int search1_launch(uttt_engine *e, int32_t resume) {
 
 int uttt_search1_begin(uttt_engine_t *e, const uttt_state_t *root, int32_t sims, int32_t batch, int32_t semantics,
                        float temperature) {
-    if (!e || !root || (semantics != UTTT_SEMANTICS_CPP && semantics != UTTT_SEMANTICS_PY)) {
-        set_error("uttt_search1_begin: bad arguments (semantics 0 = cpp, 1 = py)");
-        return UTTT_ERR_ARG;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc0 = search1_stop(e)) return rc0;
-    int rc = search_begin_common(e, 1, sims, batch);
-    if (rc) return rc;
-    e->tr.py = semantics == UTTT_SEMANTICS_PY ? 1 : 0;
-    e->selfplay = false;
+    // (search_begin_common: a resident wave left by an unfinished search exits first)
+    if (int rc = begin_with_semantics(e, "uttt_search1_begin", root, 1, sims, batch, semantics)) return rc;
     const int32_t need = e->tr.batch > 16 ? e->tr.batch : 16;  // rows per flush: 1 or k <= batch
-    if (need > e->s1_cap) {
-        if (e->h_s1) (void)hipHostFree(e->h_s1);  // no wave is resident (search1_stop)
+    if (need > e->s1_cap) {  // no wave is resident
+        const int64_t bytes = (int64_t)(sizeof(Search1Host) + (size_t)need * 97 * sizeof(float) + 16);
         e->h_s1 = nullptr;
-        e->s1_cap = 0;
-        const size_t bytes = sizeof(Search1Host) + (size_t)need * 97 * sizeof(float) + 16;
-        if (hipHostMalloc((void **)&e->h_s1, bytes, hipHostMallocCoherent) != hipSuccess) {
-            set_error("hipHostMalloc failed");
-            return UTTT_ERR_HIP;
-        }
-        memset((void *)e->h_s1, 0, bytes);
-        e->s1_cap = need;
+        if (int rc = grow_group(e->s1_cap, need, e->s1_mem, bytes)) return rc;
+        memset(e->s1_mem, 0, (size_t)bytes);
+        e->h_s1 = reinterpret_cast<Search1Host *>(e->s1_mem.get());
     }
     Search1Host *h = e->h_s1;
     h->tag = 0;
@@ -3361,35 +3334,20 @@ int uttt_search1_next(uttt_engine_t *e, uttt_state_t *leaf, int32_t *copies, int
     }
     const int32_t want = e->s1_seq + 1;
     Search1Host *h = e->h_s1;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 1;; ++it) {
-        if (__atomic_load_n(&h->tag, __ATOMIC_ACQUIRE) == want) break;
-        // the stream is queried only for a wait past 20 ms (the wave's 100 ms timeout, a failed stream): a
-        // query goes through the runtime's locks (uttt_rounds_hash_move)
-        if ((it & 255u) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-                set_error("engine stream failed: %s", hipGetErrorString(q));
+    const int rc = spin_wait(
+        e, "one-tree search result", [&] { return __atomic_load_n(&h->tag, __ATOMIC_ACQUIRE) == want; },
+        [&]() -> int {
+            // the wave timed out waiting for the previous command (the host took over 100 ms): resume it,
+            // the command it did not see applied first
+            if (__atomic_load_n(&h->gone, __ATOMIC_ACQUIRE) != e->s1_seq || e->s1_seq == 0) {
+                set_error("engine: the resident search left without storing its result");
                 return UTTT_ERR_HIP;
             }
-            if (q == hipSuccess && __atomic_load_n(&h->tag, __ATOMIC_ACQUIRE) != want) {
-                // the wave timed out waiting for the previous command (the host took over 100 ms): resume it,
-                // the command it did not see applied first
-                if (__atomic_load_n(&h->gone, __ATOMIC_ACQUIRE) != e->s1_seq || e->s1_seq == 0) {
-                    set_error("engine: the resident search left without storing its result");
-                    return UTTT_ERR_HIP;
-                }
-                h->gone = 0;
-                __atomic_thread_fence(__ATOMIC_SEQ_CST);
-                if (int rc0 = search1_launch(e, 1)) return rc0;
-            }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-                set_error("engine: one-tree search result not stored within 60 s");
-                return UTTT_ERR_HIP;
-            }
-        }
-        __builtin_ia32_pause();
-    }
+            h->gone = 0;
+            __atomic_thread_fence(__ATOMIC_SEQ_CST);
+            return search1_launch(e, 1);
+        });
+    if (rc) return rc;
     e->s1_seq = want;
     const int n = __atomic_load_n(&h->count, __ATOMIC_ACQUIRE);
     if (n > 0) {
@@ -3426,13 +3384,8 @@ int uttt_search1_apply(uttt_engine_t *e, const float *policy, int64_t pld, const
         set_error("uttt_search1_apply: %d results for a leaf queued %d times (pass 1 or %d)", rows, k, k);
         return UTTT_ERR_ARG;
     }
-    float *hp = s1_policy(e), *hv = s1_value(e);
-    for (int32_t r = 0; r < rows; ++r) {
-        memcpy(hp + (size_t)r * 96, policy + (size_t)r * pld, 81 * sizeof(float));
-        hv[r] = value[r];
-    }
-    // the rows before the command the wave polls (x86 keeps stores in order; the fence keeps the compiler's)
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    // the rows before the command the wave polls (stage_rows' fence)
+    stage_rows(s1_policy(e), s1_value(e), policy, pld, value, rows);
     __atomic_store_n(&h->cmd, (uint64_t)(uint32_t)rows << 32 | (uint32_t)e->s1_seq, __ATOMIC_RELEASE);
     e->phase = 1;
     e->n_pending = 0;
@@ -3484,9 +3437,12 @@ int uttt_search_select_host(uttt_engine_t *e, uttt_state_t *leaf, int32_t *copie
         e->launches[kKApply] += do_apply;
         timed_launch(e, kKSelect, e->tr.py ? k_flush1<true> : k_flush1<false>, dim3(1), dim3(kWave), e->pool, e->tr,
                      e->cache, a.cache, a.policy, (int64_t)96, a.value, (int64_t)1, a.rowbase, a.per_copy, do_apply,
-                     e->timing ? e->d_bytes : nullptr, e->h_leaf, tag);
+                     stats_ptr(e), e->h_leaf.get(), tag);
         if ((rc = check_launch())) return rc;
-        if ((rc = wait_host_tag(e, &e->h_leaf->tag, tag))) return rc;
+        // (spin, no stream sync; the gated stream queries only take runtime calls off this path)
+        if ((rc = spin_wait(e, "round result", [&] { return __atomic_load_n(&e->h_leaf->tag, __ATOMIC_ACQUIRE) == tag; },
+                            drained_error("engine: the stream drained without storing the round's tag"))))
+            return rc;
         n = __atomic_load_n(&e->h_leaf->count, __ATOMIC_ACQUIRE);
         if (e->timing) drain_events(e);
         if (n > 0 || __atomic_load_n(&e->h_leaf->stopped, __ATOMIC_ACQUIRE) == 0) break;
@@ -3519,24 +3475,13 @@ int uttt_search_apply_host(uttt_engine_t *e, const float *policy, int64_t pld, c
     if (rows > e->h_eval_rows) {
         // grown between rounds only: the k_flush1 that last read the buffer completed before it stored the
         // tag the host has seen
-        if (e->h_eval) (void)hipHostFree(e->h_eval);
-        e->h_eval = nullptr;
         int64_t cap = e->h_eval_rows ? e->h_eval_rows : 16;
         while (cap < rows) cap *= 2;
-        if (hipHostMalloc((void **)&e->h_eval, (size_t)cap * 97 * sizeof(float) + 16, hipHostMallocCoherent) != hipSuccess) {
-            e->h_eval_rows = 0;
-            set_error("hipHostMalloc failed");
-            return UTTT_ERR_HIP;
-        }
-        e->h_eval_rows = cap;
+        if (int rc = grow_group(e->h_eval_rows, cap, e->h_eval, cap * 97 + 4)) return rc;
         reinterpret_cast<int32_t *>(e->h_eval + cap * 97)[0] = 0;  // the per-copy row base of slot 0
     }
-    float *hp = e->h_eval, *hv = e->h_eval + e->h_eval_rows * 96;
-    for (int32_t r = 0; r < rows; ++r) {
-        memcpy(hp + (size_t)r * 96, policy + (size_t)r * pld, 81 * sizeof(float));
-        hv[r] = value[r];
-    }
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);  // before the launch that reads them
+    // the rows before the launch that reads them
+    stage_rows(e->h_eval, e->h_eval + e->h_eval_rows * 96, policy, pld, value, rows);
     e->host_apply_rows = rows;  // applied by the next k_flush1 (or flush_host_apply)
     e->phase = 1;
     e->n_pending = 0;
@@ -3659,18 +3604,11 @@ int uttt_playouts(uttt_engine_t *e, const uttt_state_t *states, int32_t n, int32
     if (n > e->po_rows) {
         int64_t rows = e->po_rows ? e->po_rows : 1024;
         while (rows < n) rows *= 2;
-        if (e->d_po_states) (void)hipFree(e->d_po_states);
-        if (e->d_po_counts) (void)hipFree(e->d_po_counts);
-        e->d_po_states = nullptr;
-        e->d_po_counts = nullptr;
-        e->po_rows = 0;
-        HIP_TRY(hipMalloc((void **)&e->d_po_states, (size_t)rows * sizeof(uttt_state_t)));
-        HIP_TRY(hipMalloc((void **)&e->d_po_counts, (size_t)rows * 2 * sizeof(int32_t)));
-        e->po_rows = rows;
+        if (int rc = grow_group(e->po_rows, rows, e->d_po_states, rows, e->d_po_counts, rows * 2)) return rc;
     }
     int32_t *d_wins = e->d_po_counts, *d_losses = e->d_po_counts + n;
     HIP_TRY(hipMemcpyAsync(e->d_po_states, states, sizeof(uttt_state_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    timed_launch(e, kKPlayout, k_playout_states, dim3(grid_waves(n)), dim3(kBlock), (const uttt_state_t *)e->d_po_states,
+    timed_launch(e, kKPlayout, k_playout_states, dim3(grid_waves(n)), dim3(kBlock), (const uttt_state_t *)e->d_po_states.get(),
                  (int)n, (int)playouts, seed, d_wins, d_losses);
     if (int rc = check_launch()) return rc;
     HIP_TRY(hipMemcpyAsync(wins, d_wins, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
@@ -3716,7 +3654,7 @@ static int round_hash_async_impl(uttt_engine *e, int32_t ring_slot, int32_t tag,
     const int apply = e->dev_apply_staged ? 1 : 0;
     timed_launch(e, kKSelect, e->tr.py ? k_round1<true> : k_round1<false>, dim3(grid_waves(e->tr.n_trees)),
                  dim3(kBlock), e->pool, e->tr, e->cache, e->dev_apply_policy, e->dev_apply_value, policy, value, apply,
-                 e->timing ? e->d_bytes : nullptr, e->h_ring + 4 * ring_slot, tag, e->d_r1ctl, part_host, part_dev,
+                 stats_ptr(e), e->h_ring + 4 * ring_slot, tag, e->d_r1ctl.get(), part_host, part_dev,
                  part_prev, nb_prev, stats_parity);
     if (int rc0 = check_launch()) return rc0;
     e->dev_apply_policy = policy;
@@ -3757,13 +3695,12 @@ int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, floa
     const int nb = grid_waves(e->tr.n_trees);
     if (parts && !e->h_part) {
         const int cap = grid_waves(e->max_trees);
-        if (hipHostMalloc((void **)&e->h_part, sizeof(uint32_t) * (size_t)kCountRing * cap, hipHostMallocCoherent) !=
-            hipSuccess) {
-            set_error("hipHostMalloc failed");
-            return UTTT_ERR_HIP;
-        }
+        if (int rc = e->h_part.grow((int64_t)kCountRing * cap)) return rc;
         memset(e->h_part, 0xFF, sizeof(uint32_t) * (size_t)kCountRing * cap);  // no word valid (n0 field 31)
-        if (int rc = alloc_n(e, &e->d_part, (size_t)2 * cap)) return rc;
+        if (int rc = alloc_n(e, e->d_part, (size_t)2 * cap)) {
+            e->h_part.reset();  // (the pair is made once, together)
+            return rc;
+        }
         e->part_cap = cap;
     }
     const int cap = e->part_cap;
@@ -3786,50 +3723,26 @@ int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, floa
         *n_with_leaves = with_leaves;
         return rc;
     };
-    // the spin's failure checks: the stream is queried only for a wait past 20 ms (a failed or finished
-    // stream): a query while the rounds run goes through the runtime's locks and cost tree-only self-play 7%
-    // when made every ~40 us (round 6)
-    auto still_waiting = [&](const std::chrono::steady_clock::time_point &t0, unsigned it, auto &&ready) -> int {
-        if ((it & 1023u) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-                set_error("engine stream failed: %s", hipGetErrorString(q));
-                return UTTT_ERR_HIP;
-            }
-            if (q == hipSuccess && !ready()) {
-                set_error("engine: a hash round ended without storing its counts");
-                return UTTT_ERR_HIP;
-            }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-                set_error("engine: a hash round's counts not stored within 60 s");
-                return UTTT_ERR_HIP;
-            }
-        }
-        __builtin_ia32_pause();
-        return UTTT_OK;
+    auto wait_counts = [&](auto &&ready) {
+        return spin_wait(e, "a hash round's counts", ready,
+                         drained_error("engine: a hash round ended without storing its counts"));
     };
     for (int32_t i = 0; i < depth; ++i)
         if (int rc = push()) return finish(rc);
     for (;;) {
         const int slot = (ring_slot + head) % kCountRing;
         const int32_t want = tag_of(head);
-        const auto t0 = std::chrono::steady_clock::now();
         int32_t n = 0, left = 0;
         if (parts) {  // every block's word carries this round's tag: sum them
             const uint32_t *pw = e->h_part + (size_t)slot * cap;
             const uint32_t want17 = (uint32_t)want & kPartTagMask;
             auto word_ok = [&](uint32_t w) { return (w >> kPartTagShift) == want17 && (w & 0x1Fu) <= 16u; };
-            int i = 0;
-            auto all_ready = [&] {
-                for (int j = 0; j < nb; ++j)
-                    if (!word_ok(__atomic_load_n(pw + j, __ATOMIC_ACQUIRE))) return false;
-                return true;
-            };
-            for (unsigned it = 1; i < nb; ++it) {
-                while (i < nb && word_ok(__atomic_load_n(pw + i, __ATOMIC_ACQUIRE))) ++i;
-                if (i < nb)
-                    if (int rc = still_waiting(t0, it, all_ready)) return finish(rc);
-            }
+            int i = 0;  // the words before i have arrived (a word stays until the host has read its round)
+            if (int rc = wait_counts([&] {
+                    while (i < nb && word_ok(__atomic_load_n(pw + i, __ATOMIC_ACQUIRE))) ++i;
+                    return i >= nb;
+                }))
+                return finish(rc);
             for (int j = 0; j < nb; ++j) {
                 const uint32_t w = __atomic_load_n(pw + j, __ATOMIC_ACQUIRE);
                 n += (int32_t)(w & 0x1Fu);
@@ -3837,9 +3750,7 @@ int uttt_rounds_hash_move(uttt_engine_t *e, int32_t ring_slot, int32_t tag, floa
             }
         } else {
             const int32_t *w = e->h_ring + 4 * slot;
-            auto ready = [&] { return __atomic_load_n(w + 3, __ATOMIC_ACQUIRE) == want; };
-            for (unsigned it = 1; !ready(); ++it)
-                if (int rc = still_waiting(t0, it, ready)) return finish(rc);
+            if (int rc = wait_counts([&] { return __atomic_load_n(w + 3, __ATOMIC_ACQUIRE) == want; })) return finish(rc);
             n = __atomic_load_n(w + 0, __ATOMIC_ACQUIRE);
             left = __atomic_load_n(w + 2, __ATOMIC_ACQUIRE);
         }
@@ -3869,15 +3780,20 @@ static int check_tree_errors(uttt_engine *e) {
     return UTTT_OK;
 }
 
-int uttt_search_root_visits(uttt_engine_t *e, int32_t *visits, int32_t *n_legal) {
+// Before a search's root results are read: a staged evaluation applied, then any failed tree reported
+static int root_results_ready(uttt_engine *e) {
     if (!e) return UTTT_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
-    if (int rc0 = flush_host_apply(e)) return rc0;
-    int rc = check_tree_errors(e);
+    if (int rc = flush_host_apply(e)) return rc;
+    return check_tree_errors(e);
+}
+
+int uttt_search_root_visits(uttt_engine_t *e, int32_t *visits, int32_t *n_legal) {
+    int rc = root_results_ready(e);
     if (rc) return rc;
     const int n = e->tr.n_trees;
-    hipLaunchKernelGGL(k_root_visits, dim3((n * 81 + 255) / 256), dim3(256), 0, e->stream, e->pool, e->tr, e->d_visits,
-                       e->d_nlegal);
+    hipLaunchKernelGGL(k_root_visits, dim3((n * 81 + 255) / 256), dim3(256), 0, e->stream, e->pool, e->tr,
+                       e->d_visits.get(), e->d_nlegal.get());
     if ((rc = check_launch())) return rc;
     if (visits)
         HIP_TRY(hipMemcpyAsync(visits, e->d_visits, sizeof(int32_t) * 81 * n, hipMemcpyDeviceToHost, e->stream));
@@ -3887,14 +3803,11 @@ int uttt_search_root_visits(uttt_engine_t *e, int32_t *visits, int32_t *n_legal)
 }
 
 int uttt_search_scores(uttt_engine_t *e, float temperature, float *scores, int32_t *n_legal) {
-    if (!e) return UTTT_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc0 = flush_host_apply(e)) return rc0;
-    int rc = check_tree_errors(e);
+    int rc = root_results_ready(e);
     if (rc) return rc;
     const int n = e->tr.n_trees;
     hipLaunchKernelGGL(k_root_scores, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->pool, e->tr, temperature,
-                       e->d_scores, e->d_nlegal);
+                       e->d_scores.get(), e->d_nlegal.get());
     if ((rc = check_launch())) return rc;
     if (scores) HIP_TRY(hipMemcpyAsync(scores, e->d_scores, sizeof(float) * 81 * n, hipMemcpyDeviceToHost, e->stream));
     if (n_legal) HIP_TRY(hipMemcpyAsync(n_legal, e->d_nlegal, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
@@ -3916,33 +3829,31 @@ int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, 
     if (rc) return rc;
     e->phase = 0;  // move_begin first
     SelfPlay &sp = e->sp;
-    if (!sp.slot) {
-        if ((rc = alloc_n(e, &sp.slot, slots)) || (rc = alloc_n(e, &sp.mt_key, (size_t)slots * 624)) ||
-            (rc = alloc_n(e, &sp.mt_pos, slots)) || (rc = alloc_n(e, &sp.ply_state, (size_t)slots * kMaxPlies)) ||
-            (rc = alloc_n(e, &sp.ply_policy, (size_t)slots * kMaxPlies * 81)) ||
-            (rc = alloc_n(e, &sp.ply_action, (size_t)slots * kMaxPlies)) || (rc = alloc_n(e, &sp.ctr, 4)) ||
-            (rc = alloc_n(e, &sp.live, slots)) || (rc = alloc_n(e, &sp.work, (size_t)slots + 1)))
+    if (!e->m_work) {  // the last of the per-slot blocks: all of them are there, or the run cannot start
+        if ((rc = alloc_n(e, e->m_slot, slots, &sp.slot)) || (rc = alloc_n(e, e->m_mt_key, (size_t)slots * 624, &sp.mt_key)) ||
+            (rc = alloc_n(e, e->m_mt_pos, slots, &sp.mt_pos)) ||
+            (rc = alloc_n(e, e->m_ply_state, (size_t)slots * kMaxPlies, &sp.ply_state)) ||
+            (rc = alloc_n(e, e->m_ply_policy, (size_t)slots * kMaxPlies * 81, &sp.ply_policy)) ||
+            (rc = alloc_n(e, e->m_ply_action, (size_t)slots * kMaxPlies, &sp.ply_action)) ||
+            (rc = alloc_n(e, e->m_ctr, 4, &sp.ctr)) || (rc = alloc_n(e, e->m_live, slots, &sp.live)) ||
+            (rc = alloc_n(e, e->m_work, (size_t)slots + 1, &sp.work)))
             return rc;
     }
     // every archived game has >= 1 ply, so the arena bounds the game table too
-    const int64_t games = std::min<int64_t>(game_end - game_begin, arena_plies);
+    const int64_t games = std::max<int64_t>(std::min<int64_t>(game_end - game_begin, arena_plies), 1);
     if (sp.arena_cap < arena_plies) {
-        if (sp.ar_state) {
-            (void)hipFree(sp.ar_state);
-            (void)hipFree(sp.ar_policy);
-            (void)hipFree(sp.ar_action);
-            (void)hipFree(sp.ar_value);
-        }
-        HIP_TRY(hipMalloc((void **)&sp.ar_state, sizeof(uttt_state_t) * arena_plies));
-        HIP_TRY(hipMalloc((void **)&sp.ar_policy, sizeof(double) * 81 * arena_plies));
-        HIP_TRY(hipMalloc((void **)&sp.ar_action, arena_plies));
-        HIP_TRY(hipMalloc((void **)&sp.ar_value, arena_plies));
-        sp.arena_cap = arena_plies;
+        rc = grow_group(sp.arena_cap, arena_plies, e->m_ar_state, arena_plies, e->m_ar_policy, 81 * arena_plies,
+                        e->m_ar_action, arena_plies, e->m_ar_value, arena_plies);
+        sp.ar_state = e->m_ar_state;  // (null after a failed growth, with arena_cap 0)
+        sp.ar_policy = e->m_ar_policy;
+        sp.ar_action = e->m_ar_action;
+        sp.ar_value = e->m_ar_value;
+        if (rc) return rc;
     }
-    if (sp.games_cap < games || !sp.games) {
-        if (sp.games) (void)hipFree(sp.games);
-        HIP_TRY(hipMalloc((void **)&sp.games, sizeof(GameEntry) * std::max<int64_t>(games, 1)));
-        sp.games_cap = std::max<int64_t>(games, 1);
+    if (sp.games_cap < games) {
+        rc = grow_group(sp.games_cap, games, e->m_games, games);
+        sp.games = e->m_games;
+        if (rc) return rc;
     }
     sp.game_end = game_end;
     sp.seed_base = seed_base;
@@ -3965,6 +3876,37 @@ int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, 
     return uttt_engine_cache_clear(e);  // a new run may use a new model
 }
 
+// A self-play move's roots: the slots' states, read in place (Slot.state is the first member)
+static int launch_move_begin(uttt_engine *e) {
+    const int slots = e->sp.slots;
+    e->dev_apply_staged = false;  // (a move that was never ended)
+    e->host_apply_rows = 0;       // (a one-tree evaluation staged by a search on this engine, never applied)
+    e->tr.n_trees = slots;
+    e->moves++;
+    hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
+                       (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err.get());
+    if (int rc = check_launch()) return rc;
+    e->phase = 1;
+    e->n_pending = 0;
+    return UTTT_OK;
+}
+
+// A move's end: k_move_end, k_finalize, k_archive. fail / ctl / err / h_move: the asynchronous form's failure
+// flag, tree controls, first-failure word and host counters (all null in the blocking form, which has checked
+// the trees and copies the counters itself)
+static int launch_move_end(uttt_engine *e, const int32_t *fail, const TreeCtl *ctl, unsigned long long *err,
+                           int64_t *h_move) {
+    const int slots = e->sp.slots;
+    {
+        TimedLaunch tl(e, kKMoveEnd);
+        hipLaunchKernelGGL(k_move_end, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->sp, fail);
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, e->stream, e->sp, fail, ctl, err, h_move);
+        hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp,
+                           (const unsigned long long *)err, 1);
+    }
+    return check_launch();
+}
+
 int uttt_selfplay_move_begin(uttt_engine_t *e, int32_t *n_live) {
     if (!e || !e->selfplay) {
         set_error("uttt_selfplay_move_begin: call uttt_selfplay_begin first");
@@ -3972,29 +3914,17 @@ int uttt_selfplay_move_begin(uttt_engine_t *e, int32_t *n_live) {
     }
     HIP_TRY(hipSetDevice(e->device));
     const int slots = e->sp.slots;
-    e->tr.n_trees = slots;
     if (e->cache.flag && e->cache_clear_every > 0 && e->moves > 0 && e->moves % e->cache_clear_every == 0) {
         int rc0 = uttt_engine_cache_clear(e);
         if (rc0) return rc0;
     }
-    e->dev_apply_staged = false;  // (a move that was never ended)
-    e->host_apply_rows = 0;       // (a one-tree evaluation staged by a search on this engine, never applied)
-    e->moves++;
-    // roots = the slots' current positions (Slot.state is the first member)
     std::vector<int32_t> live(slots);
     HIP_TRY(hipMemcpyAsync(live.data(), e->sp.live, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     int nl = 0;
     for (int v : live) nl += v != 0;
     if (n_live) *n_live = nl;
-    // roots: the slots' states, read in place (Slot.state is the first member)
-    hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
-                       (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err);
-    int rc = check_launch();
-    if (rc) return rc;
-    e->phase = 1;
-    e->n_pending = 0;
-    return UTTT_OK;
+    return launch_move_begin(e);
 }
 
 int uttt_selfplay_move_end(uttt_engine_t *e, int64_t *n_finished) {
@@ -4010,17 +3940,7 @@ int uttt_selfplay_move_end(uttt_engine_t *e, int64_t *n_finished) {
     if (int rc0 = flush_host_apply(e)) return rc0;  // a staged round's evaluation (uttt_round_hash_async)
     int rc = check_tree_errors(e);
     if (rc) return rc;
-    const int slots = e->sp.slots;
-    {
-        TimedLaunch tl(e, kKMoveEnd);
-        const unsigned long long *no_err = nullptr;
-        hipLaunchKernelGGL(k_move_end, dim3((slots + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, e->stream,
-                           e->pool, e->sp, (const int32_t *)nullptr);
-        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, e->stream, e->sp, (const int32_t *)nullptr,
-                           (const TreeCtl *)nullptr, (unsigned long long *)nullptr, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp, no_err, 1);
-    }
-    if ((rc = check_launch())) return rc;
+    if ((rc = launch_move_end(e, nullptr, nullptr, nullptr, nullptr))) return rc;
     int64_t ctr[4];
     HIP_TRY(hipMemcpyAsync(ctr, e->sp.ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4049,18 +3969,7 @@ int uttt_selfplay_move_begin_async(uttt_engine_t *e) {
         return UTTT_ERR_ORDER;
     }
     HIP_TRY(hipSetDevice(e->device));
-    const int slots = e->sp.slots;
-    e->dev_apply_staged = false;  // (a move that was never ended)
-    e->host_apply_rows = 0;       // (a one-tree evaluation staged by a search on this engine, never applied)
-    e->tr.n_trees = slots;
-    e->moves++;
-    hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
-                       (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err);
-    int rc = check_launch();
-    if (rc) return rc;
-    e->phase = 1;
-    e->n_pending = 0;
-    return UTTT_OK;
+    return launch_move_begin(e);
 }
 
 int uttt_selfplay_move_end_async(uttt_engine_t *e) {
@@ -4074,21 +3983,10 @@ int uttt_selfplay_move_end_async(uttt_engine_t *e) {
     }
     HIP_TRY(hipSetDevice(e->device));
     if (int rc0 = flush_host_apply(e)) return rc0;  // a staged round's evaluation (uttt_round_hash_async)
-    const int slots = e->sp.slots;
-    {  // d_err and the failure flag were reset by this move's k_begin
-        TimedLaunch tl(e, kKMoveEnd);
-        // a failed tree leaves the whole move unended (the failure flag, set where a tree's status gets an
-        // error bit; k_finalize then puts the first failed tree into *d_err, which k_archive checks), so the
-        // engine is in the state the blocking move end refuses in
-        const int32_t *fail = e->tr.count + 3;
-        const unsigned long long *err = e->d_err;
-        hipLaunchKernelGGL(k_move_end, dim3((slots + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, e->stream,
-                           e->pool, e->sp, fail);
-        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, e->stream, e->sp, fail, (const TreeCtl *)e->tr.ctl,
-                           e->d_err, e->h_move);
-        hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp, err, 1);
-    }
-    int rc = check_launch();
+    // d_err and the failure flag were reset by this move's k_begin. A failed tree leaves the whole move unended
+    // (the failure flag, set where a tree's status gets an error bit; k_finalize then puts the first failed tree
+    // into *d_err, which k_archive checks), so the engine is in the state the blocking move end refuses in
+    int rc = launch_move_end(e, e->tr.count + 3, e->tr.ctl, e->d_err, e->h_move);
     if (rc) return rc;  // k_finalize stored the counters and the failure word into h_move
     e->phase = 0;
     return UTTT_OK;
@@ -4190,20 +4088,23 @@ int uttt_engine_set_cache(uttt_engine_t *e, int32_t log2_capacity, int32_t clear
     }
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->cache.flag && e->cache_owner) {
-        (void)hipFree(e->cache.flag);
-        (void)hipFree(e->cache.rec);
-        e->bytes -= (int64_t)((sizeof(uint32_t) + kRecBytes) << e->cache_log2);
-    }
+    // this engine's own table goes (a shared one is only a view: nothing to free)
+    e->bytes -= (int64_t)((sizeof(uint32_t) + kRecBytes) * (size_t)e->m_cache_flag.cap());
+    e->m_cache_flag.reset();
+    e->m_cache_rec.reset();
     e->cache = EvalCache{};
     e->cache_owner = true;
-    e->cache_log2 = log2_capacity;
+    e->cache_log2 = 0;
     e->cache_clear_every = clear_every_moves;
     if (log2_capacity == 0) return UTTT_OK;
-    const size_t cap = (size_t)1 << log2_capacity;
-    HIP_TRY(hipMalloc((void **)&e->cache.flag, sizeof(uint32_t) * cap));
-    HIP_TRY(hipMalloc((void **)&e->cache.rec, (size_t)kRecBytes * cap));
-    e->bytes += (int64_t)((sizeof(uint32_t) + kRecBytes) * cap);
+    int64_t cap = 0;
+    if (int rc = grow_group(cap, (int64_t)1 << log2_capacity, e->m_cache_flag, (int64_t)1 << log2_capacity,
+                            e->m_cache_rec, (int64_t)kRecBytes << log2_capacity))
+        return rc;
+    e->cache_log2 = log2_capacity;
+    e->bytes += (int64_t)((sizeof(uint32_t) + kRecBytes) * (size_t)cap);
+    e->cache.flag = e->m_cache_flag;
+    e->cache.rec = e->m_cache_rec;
     e->cache.mask = (uint32_t)(cap - 1);
     e->cache.ctr = e->d_cache_ctr;
     return uttt_engine_cache_clear(e);
