@@ -96,6 +96,28 @@ int uttt_boltzman(const float *xs, int32_t n, float temperature, float *out);
  * uttt_eval_playout_dev compute on the device, bit for bit. */
 int uttt_playout_host(const uttt_state_t *states, int64_t n, int32_t playouts, uint64_t seed, int32_t *wins,
                       int32_t *losses);
+/* alpha_beta / alpha_beta_action — game.py:240-274, for n late positions: the exact value of each position for
+ * its side to move and of each of its legal moves. One full-depth fail-hard negamax (values -1 / 0 / +1,
+ * window (-1, +1), moves ascending) per legal action a, on the child next(s, a); each of these searches
+ * counts the nodes it visits and stops unsolved at max_nodes (1..2^22) (csrc/uttt_solve.h).
+ *   action_values[i*81 + a]: minus the child's value; UTTT_SOLVE_UNKNOWN for an unsolved child and for an
+ *     illegal action.
+ *   status[i]: UTTT_SOLVE_SOLVED when some solved move wins (value +1, action the lowest such move; other
+ *     moves may be unknown) or every move is solved (value the largest action value, action the lowest move
+ *     that reaches it: alpha_beta_action's choice); UTTT_SOLVE_BUDGET otherwise (value 0, action -1).
+ *     A terminal position is SOLVED with value -1 (lost) or 0 (drawn), action -1, nodes 0. A position that
+ *     is not terminal and has more than 32 empty cells in open small boards is not searched:
+ *     UTTT_SOLVE_TOO_LARGE, value 0, action -1, nodes 0.
+ *   nodes[i]: nodes visited over all of the position's moves.
+ * value, action, status: int8[n]; nodes: int64[n]; action_values: int8[n*81]; any of them may be NULL.
+ * Pure CPU: what uttt_solve computes on the device, bit for bit. */
+#define UTTT_SOLVE_SOLVED 1
+#define UTTT_SOLVE_BUDGET 2
+#define UTTT_SOLVE_TOO_LARGE 3
+#define UTTT_SOLVE_UNKNOWN (-128)
+#define UTTT_SOLVE_MAX_EMPTY 32
+int uttt_solve_host(const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value, int8_t *action,
+                    int8_t *status, int64_t *nodes, int8_t *action_values);
 
 /* --------------------------------------------------------------- engine --- */
 typedef struct uttt_engine uttt_engine_t;
@@ -227,6 +249,11 @@ int uttt_eval_playout_dev(uttt_engine_t *eng, int32_t playouts, uint64_t seed, f
  * states, wins, losses: host memory. Independent of any search in progress. */
 int uttt_playouts(uttt_engine_t *eng, const uttt_state_t *states, int32_t n, int32_t playouts, uint64_t seed,
                   int32_t *wins, int32_t *losses);
+/* uttt_solve_host on the device (game.py:240-274 for n positions at once), one wave per position and one
+ * lane per legal move: copies the states in, runs on the engine's stream, copies the results out and
+ * synchronises. All pointers are host memory; any output may be NULL. Independent of any search in progress. */
+int uttt_solve(uttt_engine_t *eng, const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value,
+               int8_t *action, int8_t *status, int64_t *nodes, int8_t *action_values);
 /* One whole round with the hash evaluator, enqueued by one call (round 5; the rounds of
  * SelfPlay.steps with HashEvaluator lanes, i.e. the kernel microbenchmark of SURVEY §8(d)):
  * uttt_search_select_async_tag(ring_slot, tag) -> uttt_eval_hash_dev(policy, value) ->
@@ -329,7 +356,7 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* ------------------------------------------------------------ telemetry --- */
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
-/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout.
+/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

@@ -35,6 +35,7 @@
 #include "uttt_bits.h"
 #include "uttt_engine.h"
 #include "uttt_playout.h"
+#include "uttt_solve.h"
 
 namespace uttt {
 
@@ -91,6 +92,7 @@ enum KernelId {
     // each round folds the previous round's rows at its start, so no round needs a last block
     kKSelMaxB, kKSelTripMaxB,
     kKPlayout,  // k_playout_leaves / k_playout_states launches
+    kKSolve,    // k_solve_states launches
     kKernelCount
 };
 
@@ -1988,6 +1990,95 @@ __global__ __launch_bounds__(kBlock) void k_playout_states(const uttt_state_t *_
     }
 }
 
+// ------------------------------------------------------------------ solver --
+// Exact endgame values (uttt_solve.h; game.py:240-274 `alpha_beta` / `alpha_beta_action`): one wave per
+// position, lane i searches the child of the i-th legal action. The position is wave-uniform; each lane keeps
+// the node it is at in registers and its frames in LDS, frame d of lane l at word d * 64 + l of the wave's
+// block: whatever depths the lanes are at, lane l reads and writes bank l % 64 only, so no step has a bank
+// conflict (lane-contiguous stacks of 32 words put every second lane at one depth on one bank). One trip of the loop is
+// one step of the machine for every live lane; the wave leaves with its last lane. No atomics, no scratch;
+// each wave writes its own position's outputs only.
+struct LdsStack {
+    uint32_t *base;  // this lane's frame 0
+    __device__ __forceinline__ uint32_t load(int d) const { return base[d * kWave]; }
+    __device__ __forceinline__ void store(int d, uint32_t x) { base[d * kWave] = x; }
+};
+static_assert(sizeof(uint32_t) * kWavesPerBlock * kSolveMaxEmpty * kWave <= 65536, "k_solve_states: LDS per workgroup");
+
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// Legal actions below action j: the lane that searched j, when j is legal.
+__device__ __forceinline__ int legal_rank(const uint32_t m[3], int j) {
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+        const int k = j - 27 * w;
+        r += (int)popc32(k <= 0 ? 0u : (k >= 27 ? m[w] : m[w] & ((1u << k) - 1u)));
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_solve_states(const uttt_state_t *__restrict__ states, int n,
+                                                         int32_t max_nodes, int8_t *__restrict__ value,
+                                                         int8_t *__restrict__ action, int8_t *__restrict__ status,
+                                                         int64_t *__restrict__ nodes,
+                                                         int8_t *__restrict__ action_values) {
+    __shared__ uint32_t frames[kWavesPerBlock * kSolveMaxEmpty * kWave];
+    const int row = wave_index();
+    if (row >= n) return;
+    const int lane = lane_id();
+    const uttt_state_t s = states[row];
+    uint32_t m[3];
+    legal_mask(s, m);
+    int8_t st, val;
+    int act = -1, total = 0;
+    int av = UTTT_SOLVE_UNKNOWN;  // this lane's action value
+    if (!solve_root(s, m, st, val)) {
+        const int L = (int)(popc32(m[0]) + popc32(m[1]) + popc32(m[2]));  // <= empties(s) <= 64
+        const bool mine = lane < L;
+        SolveLane ln;
+        solve_lane_begin(ln, next_state(s, mine ? nth_legal(m, (uint32_t)lane) : 0));
+        ln.live = mine;
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        LdsStack stack{frames + wave * (kSolveMaxEmpty * kWave) + lane};
+        while (__ballot(ln.live != 0) != 0ull) {
+            if (ln.live) solve_step(ln, stack, max_nodes);
+        }
+        const bool known = mine && ln.solved;
+        if (known) av = -ln.v;
+        total = wave_sum_i(mine ? ln.nodes : 0);  // <= 64 * 2^22
+        const int best = wave_max_i(known ? av : -2);
+        const bool every = __ballot(mine && !ln.solved) == 0ull;
+        if (best == 1 || every) {
+            st = UTTT_SOLVE_SOLVED;
+            val = (int8_t)best;
+            act = nth_legal(m, (uint32_t)(__ffsll((long long)__ballot(known && av == best)) - 1));
+        }
+    }
+    // action j's value sits in lane legal_rank(j)
+    const int j1 = 64 + lane;
+    const int v0 = __shfl(av, legal_rank(m, lane) & (kWave - 1));
+    const int v1 = __shfl(av, legal_rank(m, j1 < 81 ? j1 : 80) & (kWave - 1));
+    int8_t *out = action_values + (size_t)row * 81;
+    out[lane] = (int8_t)(bit_of(m, lane) ? v0 : UTTT_SOLVE_UNKNOWN);
+    if (j1 < 81) out[j1] = (int8_t)(bit_of(m, j1) ? v1 : UTTT_SOLVE_UNKNOWN);
+    if (lane == 0) {
+        value[row] = val;
+        action[row] = (int8_t)act;
+        status[row] = st;
+        nodes[row] = (int64_t)total;
+    }
+}
+
 __global__ void k_root_visits(Pool pool, Trees tr, int32_t *visits, int32_t *n_legal) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= tr.n_trees * 81) return;
@@ -2747,6 +2838,10 @@ struct uttt_engine {
     DevBuf<uttt_state_t> d_po_states;  // uttt_playouts: the positions and their [wins | losses], one group
     DevBuf<int32_t> d_po_counts;
     int64_t po_rows = 0;
+    DevBuf<uttt_state_t> d_sv_states;  // uttt_solve: the positions, their [value | action | status | 81 action
+    DevBuf<int8_t> d_sv_out;           // values] bytes and their node counts, one group
+    DevBuf<int64_t> d_sv_nodes;
+    int64_t sv_rows = 0;
     DevBuf<float> d_scores;
     DevBuf<int32_t> d_nlegal, d_visits;
     // uttt_engine_device_bytes: what alloc_n allocated plus the engine's own cache table, as before the buffers
@@ -3613,6 +3708,37 @@ int uttt_playouts(uttt_engine_t *e, const uttt_state_t *states, int32_t n, int32
     if (int rc = check_launch()) return rc;
     HIP_TRY(hipMemcpyAsync(wins, d_wins, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(losses, d_losses, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    drain_events(e);
+    return UTTT_OK;
+}
+
+int uttt_solve(uttt_engine_t *e, const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value,
+               int8_t *action, int8_t *status, int64_t *nodes, int8_t *action_values) {
+    if (!e) return UTTT_ERR_ARG;
+    if (int rc = solve_check_args("uttt_solve", states, n, max_nodes)) return rc;
+    if (n == 0) return UTTT_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (n > e->sv_rows) {
+        int64_t rows = e->sv_rows ? e->sv_rows : 1024;
+        while (rows < n) rows *= 2;
+        if (int rc = grow_group(e->sv_rows, rows, e->d_sv_states, rows, e->d_sv_out, rows * 84, e->d_sv_nodes, rows))
+            return rc;
+    }
+    int8_t *d_value = e->d_sv_out, *d_action = d_value + n, *d_status = d_action + n, *d_av = d_status + n;
+    HIP_TRY(hipMemcpyAsync(e->d_sv_states, states, sizeof(uttt_state_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    timed_launch(e, kKSolve, k_solve_states, dim3(grid_waves((int)n)), dim3(kBlock),
+                 (const uttt_state_t *)e->d_sv_states.get(), (int)n, max_nodes, d_value, d_action, d_status,
+                 e->d_sv_nodes.get(), d_av);
+    if (int rc = check_launch()) return rc;
+    const auto out = [&](void *dst, const void *src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+    };
+    HIP_TRY(out(value, d_value, (size_t)n));
+    HIP_TRY(out(action, d_action, (size_t)n));
+    HIP_TRY(out(status, d_status, (size_t)n));
+    HIP_TRY(out(nodes, e->d_sv_nodes.get(), sizeof(int64_t) * (size_t)n));
+    HIP_TRY(out(action_values, d_av, (size_t)n * 81));
     HIP_TRY(hipStreamSynchronize(e->stream));
     drain_events(e);
     return UTTT_OK;

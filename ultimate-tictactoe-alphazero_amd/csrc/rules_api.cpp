@@ -10,6 +10,7 @@
 #include "uttt_bits.h"
 #include "uttt_engine.h"
 #include "uttt_playout.h"
+#include "uttt_solve.h"
 
 namespace uttt {
 // Last error of the calling thread, for every entry point of the C ABI (uttt_last_error).
@@ -23,6 +24,25 @@ void set_error(const char *fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_err = buf;
+}
+
+// The argument checks uttt_solve_host and uttt_solve share.
+int solve_check_args(const char *who, const uttt_state_t *states, int64_t n, int32_t max_nodes) {
+    if (n < 0 || n > kSolveMaxStates || (!states && n > 0)) {
+        set_error("%s: null states, or a count outside 0..%lld", who, (long long)kSolveMaxStates);
+        return UTTT_ERR_ARG;
+    }
+    if (max_nodes < 1 || max_nodes > kSolveMaxNodes) {
+        set_error("max_nodes must be 1..%d (got %d)", kSolveMaxNodes, max_nodes);
+        return UTTT_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (states[i].active < -1 || states[i].active > 8) {
+            set_error("active_board must be -1..8 (state %lld has %d)", (long long)i, states[i].active);
+            return UTTT_ERR_ARG;
+        }
+    }
+    return UTTT_OK;
 }
 }  // namespace uttt
 
@@ -204,6 +224,65 @@ int uttt_playout_host(const uttt_state_t *states, int64_t n, int32_t playouts, u
         }
         wins[i] = nw;
         losses[i] = nl;
+    }
+    return UTTT_OK;
+}
+
+namespace {
+struct HostStack {  // the host's frames: a local array (the device's are LDS)
+    uint32_t f[kSolveMaxEmpty];
+    uint32_t load(int d) const { return f[d]; }
+    void store(int d, uint32_t x) { f[d] = x; }
+};
+}  // namespace
+
+int uttt_solve_host(const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value, int8_t *action,
+                    int8_t *status, int64_t *nodes, int8_t *action_values) {
+    // game.py:240-274 as uttt_solve.h defines it, the lanes one after another; what k_solve_states computes.
+    if (int rc = solve_check_args("uttt_solve_host", states, n, max_nodes)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const uttt_state_t &s = states[i];
+        uint32_t m[3];
+        legal_mask(s, m);
+        int8_t av[81];
+        std::memset(av, UTTT_SOLVE_UNKNOWN, sizeof(av));
+        int8_t st, val, act = -1;
+        int64_t total = 0;
+        if (!solve_root(s, m, st, val)) {
+            bool all = true;
+            int best = -2, best_a = -1, win_a = -1;
+            for (int a = next_legal_after(m, -1); a >= 0; a = next_legal_after(m, a)) {
+                SolveLane ln;
+                HostStack stack;
+                solve_lane_begin(ln, next_state(s, a));
+                while (ln.live) solve_step(ln, stack, max_nodes);
+                total += ln.nodes;
+                if (!ln.solved) {
+                    all = false;
+                    continue;
+                }
+                av[a] = (int8_t)-ln.v;
+                if (av[a] > best) {
+                    best = av[a];
+                    best_a = a;
+                }
+                if (av[a] == 1 && win_a < 0) win_a = a;
+            }
+            if (win_a >= 0) {
+                st = UTTT_SOLVE_SOLVED;
+                val = 1;
+                act = (int8_t)win_a;
+            } else if (all) {
+                st = UTTT_SOLVE_SOLVED;
+                val = (int8_t)best;
+                act = (int8_t)best_a;
+            }
+        }
+        if (value) value[i] = val;
+        if (action) action[i] = act;
+        if (status) status[i] = st;
+        if (nodes) nodes[i] = total;
+        if (action_values) std::memcpy(action_values + i * 81, av, sizeof(av));
     }
     return UTTT_OK;
 }

@@ -4,7 +4,9 @@ Python-search semantics and the fused HIP evaluator) against the random player, 
 games alternating the first move, printing "VS_Random <average point>" for the training monitors.
 The alpha-beta and plain-MCTS opponents are disabled in the reference (:87-95); the plain-MCTS one is
 available here behind EP_VS_MCTS (off by default: the output is the reference's), as a batched search over
-random playouts on the engine (uttt_amd.PlayoutEvaluator), and as mcts_action_factory for single moves."""
+random playouts on the engine (uttt_amd.PlayoutEvaluator), and as mcts_action_factory for single moves; the
+alpha-beta one behind EP_VS_ALPHABETA (off by default too), as alpha_beta_action_factory: the engine's exact
+endgame solver where the position is small enough, a fallback player before that."""
 import os
 import random
 import sys
@@ -21,6 +23,7 @@ from uttt_amd.model import DualNetwork  # noqa: E402
 CPP_GAME_AVAILABLE = True
 EP_GAME_COUNT = 10
 EP_VS_MCTS = False  # also print "VS_MCTS <average point>" (evaluate_best_player.py:93-95, commented out there)
+EP_VS_ALPHABETA = False  # also print "VS_AlphaBeta <average point>" (evaluate_best_player.py:89-91, likewise)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 first_player_point = arena.first_player_point
@@ -46,6 +49,26 @@ def mcts_action_factory(evaluate_count=1000, playouts=64, seed=0):
         return state.legal_actions()[ns.index(max(ns))]
 
     return mcts_action
+
+
+def alpha_beta_action_factory(max_nodes=65536, fallback=None):
+    """game.py:262-274's alpha_beta_action where it finishes: next_action(state) returns the exact solver's
+    action (Engine.solve: the lowest move of the largest game-theoretic value, alpha_beta_action's choice)
+    when the position is solved within max_nodes nodes per move, else fallback(state) (default:
+    mcts_action_factory(), created on first use)."""
+    from uttt_amd import Engine, solver
+    engine = Engine(1)
+    players = {"fallback": fallback}
+
+    def alpha_beta_action(state):
+        _, action, status, _, _ = engine.solve([state], max_nodes)
+        if status[0] == solver.SOLVED and action[0] >= 0:
+            return int(action[0])
+        if players["fallback"] is None:
+            players["fallback"] = mcts_action_factory()
+        return players["fallback"](state)
+
+    return alpha_beta_action
 
 
 def play(next_actions):
@@ -79,6 +102,8 @@ def evaluate_best_player():
     if EP_VS_MCTS:
         print("VS_MCTS", arena.evaluate_vs_playouts(model, EP_GAME_COUNT, evaluate_count=pv_mcts.PV_EVALUATE_COUNT,
                                                     batch_size=pv_mcts.MCTS_BATCH_SIZE)[0])
+    if EP_VS_ALPHABETA:
+        evaluate_algorithm_of("VS_AlphaBeta", (next_pv_mcts_action, alpha_beta_action_factory()))
     del model
     return point
 

@@ -17,7 +17,7 @@ UTTT_OK = 0
 ERRORS = {-1: "UTTT_ERR_ARG", -2: "UTTT_ERR_HIP", -3: "UTTT_ERR_CAPACITY", -4: "UTTT_ERR_ORDER",
           -5: "UTTT_ERR_NODEVICE", -6: "UTTT_ERR_NONFINITE"}
 
-KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15,
+KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15, "solve": 16,
            # select latency counters (their value is in "bytes"; no launches)
            "select_levels": 6, "select_trees": 7, "select_max_levels_sum": 9,
            "select_trips": 10, "select_max_trips_sum": 12}
@@ -43,6 +43,7 @@ _F32P = ctypes.POINTER(ctypes.c_float)
 _F64P = ctypes.POINTER(ctypes.c_double)
 _U32P = ctypes.POINTER(ctypes.c_uint32)
 _U64 = ctypes.c_uint64
+_I8P = ctypes.POINTER(ctypes.c_int8)
 _SP = ctypes.POINTER(UtttState)
 
 # name -> (restype, argtypes)
@@ -63,6 +64,7 @@ SIGNATURES = {
     "uttt_state_to_string": (ctypes.c_int, [_SP, ctypes.c_char_p, _I32]),
     "uttt_boltzman": (ctypes.c_int, [_F32P, _I32, _F32, _F32P]),
     "uttt_playout_host": (ctypes.c_int, [_SP, _I64, _I32, _U64, _I32P, _I32P]),
+    "uttt_solve_host": (ctypes.c_int, [_SP, _I64, _I32, _I8P, _I8P, _I8P, _I64P, _I8P]),
     "uttt_engine_create": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_P)]),
     "uttt_engine_destroy": (ctypes.c_int, [_P]),
     "uttt_engine_share_cache": (ctypes.c_int, [_P, _P]),
@@ -86,6 +88,7 @@ SIGNATURES = {
     "uttt_eval_hash_dev": (ctypes.c_int, [_P, _P, _P]),
     "uttt_eval_playout_dev": (ctypes.c_int, [_P, _I32, _U64, _P, _P]),
     "uttt_playouts": (ctypes.c_int, [_P, _SP, _I32, _I32, _U64, _I32P, _I32P]),
+    "uttt_solve": (ctypes.c_int, [_P, _SP, _I64, _I32, _I8P, _I8P, _I8P, _I64P, _I8P]),
     "uttt_round_hash_async": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "uttt_rounds_hash_async": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32]),
     "uttt_rounds_hash_move": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, _P]),

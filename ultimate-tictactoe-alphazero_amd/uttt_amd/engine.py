@@ -200,6 +200,13 @@ class Engine:
                                      ptr(losses, ctypes.c_int32)))
         return wins, losses
 
+    def solve(self, states, max_nodes=65536):
+        """(value, action, status, nodes, action_values) of each state by exact search on the device
+        (uttt_solve; game.py:240-274 for many late positions at once): int8 arrays, nodes int64, action_values
+        (n, 81) int8. status is solver.SOLVED / BUDGET / TOO_LARGE; see solver.solve_host for the CPU's."""
+        from . import solver
+        return solver.solve_with(lambda *a: self.lib.uttt_solve(self.h, *a), states, max_nodes)
+
     def rounds_hash_async(self, ring_slot, policy, value, n_rounds):
         """n_rounds consecutive hash rounds in one call (uttt_rounds_hash_async): ring slots ring_slot ..
         ring_slot + n_rounds - 1 (mod 8), tags tag + 1 .. tag + n_rounds; returns the last round's tag."""
