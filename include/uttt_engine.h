@@ -118,6 +118,24 @@ int uttt_playout_host(const uttt_state_t *states, int64_t n, int32_t playouts, u
 #define UTTT_SOLVE_MAX_EMPTY 32
 int uttt_solve_host(const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value, int8_t *action,
                     int8_t *status, int64_t *nodes, int8_t *action_values);
+/* Exact endgame values laid over evaluator rows (csrc/uttt_solve.h). For position i and its
+ * caller-filled row (policy + i * policy_ld: 81 f32 by action; value[i * value_ld]):
+ *   more than max_empties (0..UTTT_SOLVE_MAX_EMPTY) empty cells in open small boards: UTTT_OVERLAY_SKIPPED,
+ *     nothing searched, the row untouched;
+ *   otherwise the position is solved as uttt_solve_host solves it, with max_nodes (1..2^22) per legal move.
+ *     Not SOLVED: UTTT_SOLVE_BUDGET, the row untouched. SOLVED: UTTT_SOLVE_SOLVED and value = (float)v; with
+ *     UTTT_PRIORS_OPTIMAL the policy becomes 1.0f on every legal action whose known value equals v and 0.0f on
+ *     the other entries (a position won early marks its known winning moves only, a lost one every move; a
+ *     terminal position keeps its policy), which the apply's legal mask and renormalisation make 1 / count.
+ *     UTTT_PRIORS_KEEP leaves the policy as it is.
+ * status: int8[n], may be NULL. policy_ld >= 81. Pure CPU: what uttt_eval_solve_dev computes on the device,
+ * bit for bit. */
+#define UTTT_OVERLAY_SKIPPED 0
+#define UTTT_PRIORS_KEEP 0
+#define UTTT_PRIORS_OPTIMAL 1
+int uttt_solve_overlay_host(const uttt_state_t *states, int64_t n, int32_t max_empties, int32_t max_nodes,
+                            int32_t priors, float *policy, int64_t policy_ld, float *value, int64_t value_ld,
+                            int8_t *status);
 
 /* --------------------------------------------------------------- engine --- */
 typedef struct uttt_engine uttt_engine_t;
@@ -254,6 +272,17 @@ int uttt_playouts(uttt_engine_t *eng, const uttt_state_t *states, int32_t n, int
  * synchronises. All pointers are host memory; any output may be NULL. Independent of any search in progress. */
 int uttt_solve(uttt_engine_t *eng, const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value,
                int8_t *action, int8_t *status, int64_t *nodes, int8_t *action_values);
+/* uttt_solve_overlay_host on the round's pending leaves (the count read on the device, as
+ * uttt_eval_playout_dev; after uttt_search_select or uttt_search_select_async), run after any evaluator has
+ * filled the rows and before the apply: row r of policy (at policy + r * policy_ld, policy_ld >= 81) and
+ * value[r * value_ld] get the exact value, and with UTTT_PRIORS_OPTIMAL the marks of the optimal moves, of
+ * every leaf with at most max_empties empties that max_nodes per move proves; the other rows keep what the
+ * evaluator wrote. status: int8 per row (device memory), may be NULL. One wave per leaf on the engine's
+ * stream. The overlay is a function of the position and the three parameters alone, so a search stays exact
+ * under the evaluation cache as long as the parameters do not change while a table is warm (clear it when
+ * they do). One row per leaf: per-copy applies are out of scope. */
+int uttt_eval_solve_dev(uttt_engine_t *eng, int32_t max_empties, int32_t max_nodes, int32_t priors, float *policy,
+                        int64_t policy_ld, float *value, int64_t value_ld, int8_t *status);
 /* One whole round with the hash evaluator, enqueued by one call (round 5; the rounds of
  * SelfPlay.steps with HashEvaluator lanes, i.e. the kernel microbenchmark of SURVEY §8(d)):
  * uttt_search_select_async_tag(ring_slot, tag) -> uttt_eval_hash_dev(policy, value) ->
@@ -356,7 +385,8 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* ------------------------------------------------------------ telemetry --- */
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
-/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve.
+/* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve,
+ * 17 solve_leaves.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

@@ -93,8 +93,10 @@ enum KernelId {
     kKSelMaxB, kKSelTripMaxB,
     kKPlayout,  // k_playout_leaves / k_playout_states launches
     kKSolve,    // k_solve_states launches
+    kKSolveLeaves,  // k_solve_leaves launches
     kKernelCount
 };
+static_assert(kKSolveLeaves == 17, "the public header and _lib.KERNELS state the ids");
 
 // Device counters are striped: counter i of a row lives in kStripes 128-byte slots, and a workgroup
 // adds into slot (blockIdx & (kStripes - 1)), so thousands of waves finishing together do not
@@ -2003,7 +2005,8 @@ struct LdsStack {
     __device__ __forceinline__ uint32_t load(int d) const { return base[d * kWave]; }
     __device__ __forceinline__ void store(int d, uint32_t x) { base[d * kWave] = x; }
 };
-static_assert(sizeof(uint32_t) * kWavesPerBlock * kSolveMaxEmpty * kWave <= 65536, "k_solve_states: LDS per workgroup");
+static_assert(sizeof(uint32_t) * kWavesPerBlock * kSolveMaxEmpty * kWave <= 65536,
+              "k_solve_states, k_solve_leaves: LDS per workgroup");
 
 __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
@@ -2027,6 +2030,38 @@ __device__ __forceinline__ int legal_rank(const uint32_t m[3], int j) {
     return r;
 }
 
+// The machine both solver kernels run on a searched position (solve_root said so): lane i < L searches the
+// child of the i-th legal move on this wave's block of `frames`. av: this lane's action value
+// (UTTT_SOLVE_UNKNOWN for a lane without a move or out of budget); total: the nodes of all lanes; best / every:
+// solve_result's arguments. All but av are wave-uniform.
+__device__ __forceinline__ void solve_wave(const uttt_state_t &s, const uint32_t m[3], int32_t max_nodes,
+                                           uint32_t *frames, int &av, int &total, int &best, bool &every) {
+    const int lane = lane_id();
+    const int L = (int)(popc32(m[0]) + popc32(m[1]) + popc32(m[2]));  // <= empties(s) <= 64
+    const bool mine = lane < L;
+    SolveLane ln;
+    solve_lane_begin(ln, next_state(s, mine ? nth_legal(m, (uint32_t)lane) : 0));
+    ln.live = mine;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    LdsStack stack{frames + wave * (kSolveMaxEmpty * kWave) + lane};
+    while (__ballot(ln.live != 0) != 0ull) {
+        if (ln.live) solve_step(ln, stack, max_nodes);
+    }
+    const bool known = mine && ln.solved;
+    av = known ? -ln.v : UTTT_SOLVE_UNKNOWN;
+    total = wave_sum_i(mine ? ln.nodes : 0);  // <= 64 * 2^22
+    best = wave_max_i(known ? av : -2);
+    every = __ballot(mine && !ln.solved) == 0ull;
+}
+
+// The values of actions `lane` and 64 + lane (the latter for lane < 17) from the lanes that searched them:
+// action j's value sits in lane legal_rank(j). Meaningful for legal actions only.
+__device__ __forceinline__ void action_values_of(const uint32_t m[3], int av, int &v0, int &v1) {
+    const int lane = lane_id(), j1 = 64 + lane;
+    v0 = __shfl(av, legal_rank(m, lane) & (kWave - 1));
+    v1 = __shfl(av, legal_rank(m, j1 < 81 ? j1 : 80) & (kWave - 1));
+}
+
 __global__ __launch_bounds__(kBlock) void k_solve_states(const uttt_state_t *__restrict__ states, int n,
                                                          int32_t max_nodes, int8_t *__restrict__ value,
                                                          int8_t *__restrict__ action, int8_t *__restrict__ status,
@@ -2043,31 +2078,15 @@ __global__ __launch_bounds__(kBlock) void k_solve_states(const uttt_state_t *__r
     int act = -1, total = 0;
     int av = UTTT_SOLVE_UNKNOWN;  // this lane's action value
     if (!solve_root(s, m, st, val)) {
-        const int L = (int)(popc32(m[0]) + popc32(m[1]) + popc32(m[2]));  // <= empties(s) <= 64
-        const bool mine = lane < L;
-        SolveLane ln;
-        solve_lane_begin(ln, next_state(s, mine ? nth_legal(m, (uint32_t)lane) : 0));
-        ln.live = mine;
-        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        LdsStack stack{frames + wave * (kSolveMaxEmpty * kWave) + lane};
-        while (__ballot(ln.live != 0) != 0ull) {
-            if (ln.live) solve_step(ln, stack, max_nodes);
-        }
-        const bool known = mine && ln.solved;
-        if (known) av = -ln.v;
-        total = wave_sum_i(mine ? ln.nodes : 0);  // <= 64 * 2^22
-        const int best = wave_max_i(known ? av : -2);
-        const bool every = __ballot(mine && !ln.solved) == 0ull;
-        if (best == 1 || every) {
-            st = UTTT_SOLVE_SOLVED;
-            val = (int8_t)best;
-            act = nth_legal(m, (uint32_t)(__ffsll((long long)__ballot(known && av == best)) - 1));
-        }
+        int best;
+        bool every;
+        solve_wave(s, m, max_nodes, frames, av, total, best, every);
+        if (solve_result(best, every, st, val))  // the lowest move that reaches the value (unknown lanes: -128)
+            act = nth_legal(m, (uint32_t)(__ffsll((long long)__ballot(av == best)) - 1));
     }
-    // action j's value sits in lane legal_rank(j)
     const int j1 = 64 + lane;
-    const int v0 = __shfl(av, legal_rank(m, lane) & (kWave - 1));
-    const int v1 = __shfl(av, legal_rank(m, j1 < 81 ? j1 : 80) & (kWave - 1));
+    int v0, v1;
+    action_values_of(m, av, v0, v1);
     int8_t *out = action_values + (size_t)row * 81;
     out[lane] = (int8_t)(bit_of(m, lane) ? v0 : UTTT_SOLVE_UNKNOWN);
     if (j1 < 81) out[j1] = (int8_t)(bit_of(m, j1) ? v1 : UTTT_SOLVE_UNKNOWN);
@@ -2077,6 +2096,47 @@ __global__ __launch_bounds__(kBlock) void k_solve_states(const uttt_state_t *__r
         status[row] = st;
         nodes[row] = (int64_t)total;
     }
+}
+
+// The overlay of uttt_solve.h on the round's pending leaves, shaped like k_playout_leaves (one wave per slot,
+// the count read on the device) and run after an evaluator has filled the rows: a leaf with more than
+// max_empties empties leaves at once (the test is wave-uniform: in the opening the kernel costs its launch
+// and one state load per leaf); the others run k_solve_states' machine, and a SOLVED one overwrites its
+// row's value and, with UTTT_PRIORS_OPTIMAL, its 81 priors. The same 32 KB of LDS per workgroup, no
+// scratch, no atomics; each wave writes its own row only.
+__global__ __launch_bounds__(kBlock) void k_solve_leaves(Trees tr, int32_t max_empties, int32_t max_nodes,
+                                                         int32_t priors, float *__restrict__ policy,
+                                                         int64_t policy_ld, float *__restrict__ value,
+                                                         int64_t value_ld, int8_t *__restrict__ status) {
+    __shared__ uint32_t frames[kWavesPerBlock * kSolveMaxEmpty * kWave];
+    const int row = wave_index();
+    if (row >= tr.count[0]) return;
+    const int lane = lane_id();
+    const uttt_state_t s = tr.leaf[tr.tree_of[row]];
+    int8_t st = UTTT_OVERLAY_SKIPPED, val = 0;
+    bool searched = false;
+    int av = UTTT_SOLVE_UNKNOWN;
+    uint32_t m[3] = {0u, 0u, 0u};
+    if (!overlay_skips(s, max_empties)) {
+        legal_mask(s, m);
+        searched = !solve_root(s, m, st, val);
+        if (searched) {
+            int total, best;
+            bool every;
+            solve_wave(s, m, max_nodes, frames, av, total, best, every);
+            solve_result(best, every, st, val);
+        }
+    }
+    if (status && lane == 0) status[row] = st;
+    if (st != UTTT_SOLVE_SOLVED) return;
+    if (lane == 0) value[(size_t)row * value_ld] = (float)val;
+    if (!searched || priors != UTTT_PRIORS_OPTIMAL) return;
+    const int j1 = 64 + lane;
+    int v0, v1;
+    action_values_of(m, av, v0, v1);
+    float *out = policy + (size_t)row * policy_ld;
+    out[lane] = overlay_prior(bit_of(m, lane) != 0u, v0, val);
+    if (j1 < 81) out[j1] = overlay_prior(bit_of(m, j1) != 0u, v1, val);
 }
 
 __global__ void k_root_visits(Pool pool, Trees tr, int32_t *visits, int32_t *n_legal) {
@@ -3742,6 +3802,18 @@ int uttt_solve(uttt_engine_t *e, const uttt_state_t *states, int64_t n, int32_t 
     HIP_TRY(hipStreamSynchronize(e->stream));
     drain_events(e);
     return UTTT_OK;
+}
+
+int uttt_eval_solve_dev(uttt_engine_t *e, int32_t max_empties, int32_t max_nodes, int32_t priors, float *policy,
+                        int64_t policy_ld, float *value, int64_t value_ld, int8_t *status) {
+    if (!e) return UTTT_ERR_ARG;
+    if (int rc = overlay_check_args("uttt_eval_solve_dev", max_empties, max_nodes, priors, policy, policy_ld, value,
+                                    value_ld))
+        return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    timed_launch(e, kKSolveLeaves, k_solve_leaves, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, max_empties,
+                 max_nodes, priors, policy, policy_ld, value, value_ld, status);
+    return check_launch();
 }
 
 static bool fused_rounds() {  // k_round1 (UTTT_FUSED_ROUNDS=0: the public calls' launches)

@@ -44,6 +44,37 @@ int solve_check_args(const char *who, const uttt_state_t *states, int64_t n, int
     }
     return UTTT_OK;
 }
+
+// The argument checks uttt_solve_overlay_host and uttt_eval_solve_dev share (beside solve_check_args /
+// the engine's own).
+int overlay_check_args(const char *who, int32_t max_empties, int32_t max_nodes, int32_t priors, const float *policy,
+                       int64_t policy_ld, const float *value, int64_t value_ld) {
+    if (!policy || !value) {
+        set_error("%s: null policy or value", who);
+        return UTTT_ERR_ARG;
+    }
+    if (max_empties < 0 || max_empties > kSolveMaxEmpty) {
+        set_error("max_empties must be 0..%d (got %d)", kSolveMaxEmpty, max_empties);
+        return UTTT_ERR_ARG;
+    }
+    if (max_nodes < 1 || max_nodes > kSolveMaxNodes) {
+        set_error("max_nodes must be 1..%d (got %d)", kSolveMaxNodes, max_nodes);
+        return UTTT_ERR_ARG;
+    }
+    if (priors != UTTT_PRIORS_KEEP && priors != UTTT_PRIORS_OPTIMAL) {
+        set_error("priors must be UTTT_PRIORS_KEEP (0) or UTTT_PRIORS_OPTIMAL (1) (got %d)", priors);
+        return UTTT_ERR_ARG;
+    }
+    if (policy_ld < 81) {
+        set_error("policy_ld must be at least 81 (got %lld)", (long long)policy_ld);
+        return UTTT_ERR_ARG;
+    }
+    if (value_ld < 1) {
+        set_error("value_ld must be at least 1 (got %lld)", (long long)value_ld);
+        return UTTT_ERR_ARG;
+    }
+    return UTTT_OK;
+}
 }  // namespace uttt
 
 using namespace uttt;
@@ -236,53 +267,83 @@ struct HostStack {  // the host's frames: a local array (the device's are LDS)
 };
 }  // namespace
 
+namespace {
+// One position as uttt_solve.h defines it, the lanes one after another; av: its 81 action values. Returns
+// false when the root answered without a search (terminal or too large).
+bool solve_one(const uttt_state_t &s, int32_t max_nodes, int8_t av[81], int8_t &st, int8_t &val, int8_t &act,
+               int64_t &total) {
+    uint32_t m[3];
+    legal_mask(s, m);
+    std::memset(av, UTTT_SOLVE_UNKNOWN, 81);
+    act = -1;
+    total = 0;
+    if (solve_root(s, m, st, val)) return false;
+    bool every = true;
+    int best = -2, best_a = -1;  // the lowest move that reaches the largest known value
+    for (int a = next_legal_after(m, -1); a >= 0; a = next_legal_after(m, a)) {
+        SolveLane ln;
+        HostStack stack;
+        solve_lane_begin(ln, next_state(s, a));
+        while (ln.live) solve_step(ln, stack, max_nodes);
+        total += ln.nodes;
+        if (!ln.solved) {
+            every = false;
+            continue;
+        }
+        av[a] = (int8_t)-ln.v;
+        if (av[a] > best) {
+            best = av[a];
+            best_a = a;
+        }
+    }
+    if (solve_result(best, every, st, val)) act = (int8_t)best_a;
+    return true;
+}
+}  // namespace
+
 int uttt_solve_host(const uttt_state_t *states, int64_t n, int32_t max_nodes, int8_t *value, int8_t *action,
                     int8_t *status, int64_t *nodes, int8_t *action_values) {
-    // game.py:240-274 as uttt_solve.h defines it, the lanes one after another; what k_solve_states computes.
+    // game.py:240-274 as uttt_solve.h defines it; what k_solve_states computes.
     if (int rc = solve_check_args("uttt_solve_host", states, n, max_nodes)) return rc;
     for (int64_t i = 0; i < n; ++i) {
-        const uttt_state_t &s = states[i];
-        uint32_t m[3];
-        legal_mask(s, m);
-        int8_t av[81];
-        std::memset(av, UTTT_SOLVE_UNKNOWN, sizeof(av));
-        int8_t st, val, act = -1;
-        int64_t total = 0;
-        if (!solve_root(s, m, st, val)) {
-            bool all = true;
-            int best = -2, best_a = -1, win_a = -1;
-            for (int a = next_legal_after(m, -1); a >= 0; a = next_legal_after(m, a)) {
-                SolveLane ln;
-                HostStack stack;
-                solve_lane_begin(ln, next_state(s, a));
-                while (ln.live) solve_step(ln, stack, max_nodes);
-                total += ln.nodes;
-                if (!ln.solved) {
-                    all = false;
-                    continue;
-                }
-                av[a] = (int8_t)-ln.v;
-                if (av[a] > best) {
-                    best = av[a];
-                    best_a = a;
-                }
-                if (av[a] == 1 && win_a < 0) win_a = a;
-            }
-            if (win_a >= 0) {
-                st = UTTT_SOLVE_SOLVED;
-                val = 1;
-                act = (int8_t)win_a;
-            } else if (all) {
-                st = UTTT_SOLVE_SOLVED;
-                val = (int8_t)best;
-                act = (int8_t)best_a;
-            }
-        }
+        int8_t av[81], st, val, act;
+        int64_t total;
+        solve_one(states[i], max_nodes, av, st, val, act, total);
         if (value) value[i] = val;
         if (action) action[i] = act;
         if (status) status[i] = st;
         if (nodes) nodes[i] = total;
         if (action_values) std::memcpy(action_values + i * 81, av, sizeof(av));
+    }
+    return UTTT_OK;
+}
+
+int uttt_solve_overlay_host(const uttt_state_t *states, int64_t n, int32_t max_empties, int32_t max_nodes,
+                            int32_t priors, float *policy, int64_t policy_ld, float *value, int64_t value_ld,
+                            int8_t *status) {
+    // The overlay of uttt_solve.h over n caller-filled rows; what k_solve_leaves computes.
+    if (int rc = solve_check_args("uttt_solve_overlay_host", states, n, max_nodes)) return rc;
+    if (int rc = overlay_check_args("uttt_solve_overlay_host", max_empties, max_nodes, priors, policy, policy_ld,
+                                    value, value_ld))
+        return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const uttt_state_t &s = states[i];
+        int8_t st = UTTT_OVERLAY_SKIPPED;
+        if (!overlay_skips(s, max_empties)) {
+            int8_t av[81], val, act;
+            int64_t total;
+            const bool searched = solve_one(s, max_nodes, av, st, val, act, total);
+            if (st == UTTT_SOLVE_SOLVED) {
+                value[i * value_ld] = (float)val;
+                if (searched && priors == UTTT_PRIORS_OPTIMAL) {
+                    uint32_t m[3];
+                    legal_mask(s, m);
+                    float *row = policy + i * policy_ld;
+                    for (int a = 0; a < 81; ++a) row[a] = overlay_prior(bit_of(m, a) != 0u, av[a], val);
+                }
+            }
+        }
+        if (status) status[i] = st;
     }
     return UTTT_OK;
 }

@@ -1,6 +1,6 @@
 // uttt_solve.h — exact endgame values (game.py:240-274 `alpha_beta` / `alpha_beta_action`) on the packed
 // bitboards, compiled for both the host (uttt_solve_host, the checker's counterpart) and gfx950
-// (k_solve_states). DESIGN.md §6c.
+// (k_solve_states, and k_solve_leaves inside the search's round loop). DESIGN.md §6c, §6d.
 //
 // A position is solved one legal move per lane: lane i takes the i-th legal action a in ascending order and
 // searches the child c = next_state(s, a) with a full-depth fail-hard negamax, values -1 / 0 / +1, integer
@@ -199,5 +199,35 @@ UTTT_HD bool solve_root(const uttt_state_t &s, const uint32_t m[3], int8_t &stat
     status = UTTT_SOLVE_BUDGET;
     return false;
 }
+
+// A searched position's result from what its lanes found, the one rule of the host loops and the kernels'
+// epilogues: best is the largest known action value (-2: none is known), every says that no lane ran out of
+// budget. A known winning move decides the position whatever the other lanes did; otherwise every move must
+// be known. Returns true, with status / value set, when the position is SOLVED.
+UTTT_HD bool solve_result(int best, bool every, int8_t &status, int8_t &value) {
+    if (best != 1 && !every) return false;
+    status = UTTT_SOLVE_SOLVED;
+    value = (int8_t)best;
+    return true;
+}
+
+// ----------------------------------------------------------------- overlay --
+// Exact values laid over an evaluator's rows (uttt_solve_overlay_host, k_solve_leaves). For a
+// position s, its row (policy[81], value) and the parameters max_empties, max_nodes, priors:
+//   empties(s) > max_empties: UTTT_OVERLAY_SKIPPED, nothing searched, the row untouched;
+//   otherwise s is solved as above (solve_root, one lane per legal move, solve_result). Not SOLVED: the row
+//   is untouched, status UTTT_SOLVE_BUDGET. SOLVED: value = (float)v, and with UTTT_PRIORS_OPTIMAL every
+//   policy entry becomes overlay_prior of its action, unless s is terminal (it has no move to mark).
+// With max_empties <= kSolveMaxEmpty, solve_root never answers TOO_LARGE here. The overlay does not divide:
+// the apply's legal mask and sequential renormalisation turn the marks into exactly 1 / count.
+UTTT_HD bool overlay_skips(const uttt_state_t &s, int32_t max_empties) { return empties(s) > max_empties; }
+
+// Entry a of a SOLVED, searched position's policy under UTTT_PRIORS_OPTIMAL: av is the action's known value
+// (UTTT_SOLVE_UNKNOWN when it is not known), v the position's.
+UTTT_HD float overlay_prior(bool legal, int av, int v) { return legal && av == v ? 1.0f : 0.0f; }
+
+// the argument checks of uttt_solve_overlay_host and uttt_eval_solve_dev (rules_api.cpp; host only)
+int overlay_check_args(const char *who, int32_t max_empties, int32_t max_nodes, int32_t priors, const float *policy,
+                       int64_t policy_ld, const float *value, int64_t value_ld);
 
 }  // namespace uttt

@@ -35,19 +35,25 @@ def random_action(state):
     return legal_actions[random.randint(0, len(legal_actions) - 1)]
 
 
-def mcts_action_factory(evaluate_count=1000, playouts=64, seed=0):
+def mcts_action_factory(evaluate_count=1000, playouts=64, seed=0, solve=None):
     """game.py:294-379's mcts_action on the engine: next_action(state) runs one tree of evaluate_count
     simulations whose leaves are valued by `playouts` random playouts (game.py:277-287; uniform priors, PUCT
-    in place of UCB1) and returns the first legal action with the most root visits (game.py:374-379)."""
-    from uttt_amd.selfplay import PlayoutEvaluator
+    in place of UCB1) and returns the first legal action with the most root visits (game.py:374-379).
+    solve: None, or a dict of uttt_amd.SolvedLeaves arguments (max_empties, max_nodes, priors): the leaves the
+    exact solver proves then carry their game-theoretic value; next_action.evaluator is that SolvedLeaves
+    (its solved / budget / skipped counts)."""
+    from uttt_amd.selfplay import PlayoutEvaluator, SolvedLeaves
     search = arena.PvMcts(1, max(50, evaluate_count))
     evaluator = PlayoutEvaluator(search.engine, playouts, seed)
+    if solve is not None:
+        evaluator = SolvedLeaves(evaluator, search.engine, **solve)
 
     def mcts_action(state):
         (v,) = search.visits([state], evaluator, evaluate_count, pv_mcts.MCTS_BATCH_SIZE)
         ns = [int(x) for x in v]
         return state.legal_actions()[ns.index(max(ns))]
 
+    mcts_action.evaluator = evaluator
     return mcts_action
 
 

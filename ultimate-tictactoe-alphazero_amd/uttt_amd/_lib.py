@@ -18,6 +18,7 @@ ERRORS = {-1: "UTTT_ERR_ARG", -2: "UTTT_ERR_HIP", -3: "UTTT_ERR_CAPACITY", -4: "
           -5: "UTTT_ERR_NODEVICE", -6: "UTTT_ERR_NONFINITE"}
 
 KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15, "solve": 16,
+           "solve_leaves": 17,
            # select latency counters (their value is in "bytes"; no launches)
            "select_levels": 6, "select_trees": 7, "select_max_levels_sum": 9,
            "select_trips": 10, "select_max_trips_sum": 12}
@@ -65,6 +66,7 @@ SIGNATURES = {
     "uttt_boltzman": (ctypes.c_int, [_F32P, _I32, _F32, _F32P]),
     "uttt_playout_host": (ctypes.c_int, [_SP, _I64, _I32, _U64, _I32P, _I32P]),
     "uttt_solve_host": (ctypes.c_int, [_SP, _I64, _I32, _I8P, _I8P, _I8P, _I64P, _I8P]),
+    "uttt_solve_overlay_host": (ctypes.c_int, [_SP, _I64, _I32, _I32, _I32, _F32P, _I64, _F32P, _I64, _I8P]),
     "uttt_engine_create": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_P)]),
     "uttt_engine_destroy": (ctypes.c_int, [_P]),
     "uttt_engine_share_cache": (ctypes.c_int, [_P, _P]),
@@ -89,6 +91,7 @@ SIGNATURES = {
     "uttt_eval_playout_dev": (ctypes.c_int, [_P, _I32, _U64, _P, _P]),
     "uttt_playouts": (ctypes.c_int, [_P, _SP, _I32, _I32, _U64, _I32P, _I32P]),
     "uttt_solve": (ctypes.c_int, [_P, _SP, _I64, _I32, _I8P, _I8P, _I8P, _I64P, _I8P]),
+    "uttt_eval_solve_dev": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I64, _P, _I64, _P]),
     "uttt_round_hash_async": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "uttt_rounds_hash_async": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32]),
     "uttt_rounds_hash_move": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, _P]),

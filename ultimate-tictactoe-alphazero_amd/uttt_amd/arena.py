@@ -14,7 +14,7 @@ the reference's play() after np.random.seed(seed_base + g) (same players).
 import numpy as np
 
 from .engine import as_states
-from .selfplay import BatchedSearch, NetworkEvaluator, PlayoutEvaluator
+from .selfplay import BatchedSearch, NetworkEvaluator, PlayoutEvaluator, SolvedLeaves
 
 
 def scores_from_visits(visits, temperature):
@@ -148,22 +148,30 @@ def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0
 
 def evaluate_vs_playouts(model, game_count=10, playouts=64, opponent_evaluate_count=1000, seed_base=0,
                          temperature=0.0, evaluate_count=50, batch_size=8, device=None, make_evaluator=None,
-                         playout_seed=0, progress=None):
+                         playout_seed=0, progress=None, opponent_solve=None):
     """The model's PV-MCTS player against plain MCTS over random playouts (the reference's commented-out
     VS_MCTS opponent, evaluate_best_player.py:93-95 with game.py:294-379's mcts_action: there UCB1 over one
     playout per evaluation, here the same search as the model's with PlayoutEvaluator in place of the network:
     uniform priors, the mean of `playouts` playouts as the value, opponent_evaluate_count simulations per
     move). All games run concurrently as in evaluate_network, on the Python-search semantics; the model moves
     first in even games. Returns (the model's average point, per-game first-player points, per-game action
-    lists). make_evaluator(model, engine) -> the model's engine evaluator (default as evaluate_network)."""
+    lists). make_evaluator(model, engine) -> the model's engine evaluator (default as evaluate_network).
+    opponent_solve: None, or a dict of SolvedLeaves arguments (max_empties, max_nodes, priors): the opponent
+    then plays with an exact endgame, and the result has a fourth entry, its leaf counts over all games
+    (SolvedLeaves.counts: {"skipped", "solved", "budget"})."""
     searches = [PvMcts(game_count, evaluate_count, device), PvMcts(game_count, opponent_evaluate_count, device)]
     if make_evaluator is None:
         ev = model_evaluator(model, game_count, searches[0].engine)
     else:
         ev = make_evaluator(model, searches[0].engine)
-    evaluators = (ev, PlayoutEvaluator(searches[1].engine, playouts, playout_seed))
-    return _play_games(searches, evaluators, (evaluate_count, opponent_evaluate_count), game_count, temperature,
-                       seed_base, batch_size, progress)
+    opponent = PlayoutEvaluator(searches[1].engine, playouts, playout_seed)
+    if opponent_solve is not None:
+        opponent = SolvedLeaves(opponent, searches[1].engine, **opponent_solve)
+    result = _play_games(searches, (ev, opponent), (evaluate_count, opponent_evaluate_count), game_count, temperature,
+                         seed_base, batch_size, progress)
+    if opponent_solve is not None:
+        return result + (opponent.counts(),)
+    return result
 
 
 def first_player_value(state):

@@ -207,6 +207,29 @@ class Engine:
         from . import solver
         return solver.solve_with(lambda *a: self.lib.uttt_solve(self.h, *a), states, max_nodes)
 
+    def eval_solve_dev(self, policy, value, max_empties, max_nodes, priors, status=None):
+        """Exact endgame values over the rows an evaluator filled for the round's pending leaves
+        (uttt_eval_solve_dev: states and count on the device, after select or select_async, before apply).
+        policy: (rows, >=81) f32 and value: (rows,) or (rows, 1) f32 device tensors, passed with their row
+        strides; priors: solver.PRIORS_KEEP / PRIORS_OPTIMAL; status: optional int8 device tensor, one
+        solver.SKIPPED / SOLVED / BUDGET per row."""
+        import torch
+
+        if not (policy.is_cuda and value.is_cuda and policy.dtype == torch.float32 and value.dtype == torch.float32):
+            raise ValueError("eval_solve_dev: policy and value must be float32 device tensors")
+        if policy.dim() != 2 or policy.shape[1] < 81 or policy.stride(1) != 1:
+            raise ValueError("eval_solve_dev: policy must be (rows, >=81) with unit stride along the actions")
+        if value.dim() not in (1, 2) or (value.dim() == 2 and value.shape[1] != 1) or len(value) != len(policy):
+            raise ValueError("eval_solve_dev: value must be (rows,) or (rows, 1), one per policy row")
+        if status is not None and status.numel() < len(policy):
+            raise ValueError("eval_solve_dev: status must hold one entry per row")
+        if status is not None and not (status.is_cuda and status.dtype == torch.int8 and status.is_contiguous()):
+            raise ValueError("eval_solve_dev: status must be a contiguous int8 device tensor")
+        check(self.lib.uttt_eval_solve_dev(self.h, int(max_empties), int(max_nodes), int(priors),
+                                           ctypes.c_void_p(policy.data_ptr()), policy.stride(0),
+                                           ctypes.c_void_p(value.data_ptr()), value.stride(0),
+                                           ctypes.c_void_p(status.data_ptr()) if status is not None else None))
+
     def rounds_hash_async(self, ring_slot, policy, value, n_rounds):
         """n_rounds consecutive hash rounds in one call (uttt_rounds_hash_async): ring slots ring_slot ..
         ring_slot + n_rounds - 1 (mod 8), tags tag + 1 .. tag + n_rounds; returns the last round's tag."""

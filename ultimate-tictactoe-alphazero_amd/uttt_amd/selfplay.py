@@ -94,6 +94,99 @@ class PlayoutEvaluator:
         return self.policy[:n], self.value[:n]
 
 
+class SolvedLeaves:
+    """Any evaluator with an exact endgame: after `base` has filled the round's rows, the engine lays the
+    solver's values over them (Engine.eval_solve_dev). A leaf with at most `max_empties` empty
+    cells in open boards that `max_nodes` nodes per move prove gets its exact value and, with
+    priors="optimal", priors on its optimal moves only; every other leaf keeps what `base` wrote. A function
+    of the position and these parameters alone (given that `base` is one of the position), so exact under the
+    evaluation cache: SelfPlay.set_evaluator clears the table; a BatchedSearch user who changes the parameters
+    on a cached engine calls Engine.cache_clear.
+
+    The overlay launches on the engine's stream, which in BatchedSearch and SelfPlay is the stream the
+    evaluator runs on, so it is ordered after `base` and before the apply. It has no one-call rounds:
+    SelfPlay runs it on the generic device-count loop, as it runs PlayoutEvaluator.
+
+    solved / budget / skipped: rows overlaid, searched without a proof, and not searched, over all calls.
+    The kernel writes each call's statuses into the next row of a device ring of kRing x max_trees bytes
+    prefilled with -1 (`status` is the latest call's row), so a round costs nothing beyond the overlay; the
+    rows are summed into three device totals when the ring is full (every kRing calls) and when a count is
+    read, and only a read copies anything back, on the engine's stream.
+
+    The defaults are the cheapest point of the measured sweep: a launch lasts as long as its
+    slowest lane, about 1 us per step and two steps per node, so max_nodes is the overlay's latency per round;
+    at 8 empties 256 nodes already prove all but 0.06% of the leaves searched."""
+
+    kRing = 32  # status rows kept before they are folded into the totals
+
+    def __init__(self, base, engine, max_empties=8, max_nodes=256, priors="optimal"):
+        from . import solver
+        if not 0 <= int(max_empties) <= solver.MAX_EMPTY:
+            raise ValueError(f"max_empties must be 0..{solver.MAX_EMPTY} (got {max_empties})")
+        if not 1 <= int(max_nodes) <= 1 << 22:
+            raise ValueError(f"max_nodes must be 1..{1 << 22} (got {max_nodes})")
+        self.base = base
+        self.engine = engine
+        self.max_empties = int(max_empties)
+        self.max_nodes = int(max_nodes)
+        self.priors = solver.priors_mode(priors)
+        if self.priors not in (solver.PRIORS_KEEP, solver.PRIORS_OPTIMAL):
+            raise ValueError(f"priors must be keep or optimal (got {priors!r})")
+        self.needs_input = getattr(base, "needs_input", True)
+        self.device_count = getattr(base, "device_count", False)
+        # One status row per call, kRing calls deep, every entry -1 until its call writes it (rows past the
+        # round's count stay -1): the kernel writes the statuses where the counts will later be taken from, so
+        # a round costs nothing beyond the overlay itself. The rows are folded into the totals when the ring
+        # is full and when a count is read, never per round.
+        dev = torch.device("cuda", engine.device)
+        self._ring = torch.full((self.kRing, engine.max_trees), -1, dtype=torch.int8, device=dev)
+        self._used = 0
+        self._totals = torch.zeros(3, dtype=torch.int64, device=dev)  # skipped, solved, budget
+        self.status = self._ring[0]  # the statuses of the latest call: max_trees bytes, -1 past its count
+        torch.cuda.current_stream(dev).synchronize()  # the fill, before the engine's stream writes into it
+
+    def __call__(self, x, n):
+        p, v = self.base(x, n)
+        if self._used == self.kRing:
+            self._fold()
+        self.status = self._ring[self._used]
+        self._used += 1
+        self.engine.eval_solve_dev(p, v, self.max_empties, self.max_nodes, self.priors, self.status)
+        return p, v
+
+    def _fold(self):
+        if self._used:
+            with torch.cuda.stream(self.engine.stream):  # ordered after the overlays that wrote the rows
+                rows = self._ring[:self._used]
+                self._totals += torch.stack([(rows == k).sum() for k in (0, 1, 2)])
+                rows.fill_(-1)
+            self._used = 0
+
+    def counts(self):
+        """{"skipped", "solved", "budget"}: rows of all calls so far (one read-back)."""
+        self._fold()
+        with torch.cuda.stream(self.engine.stream):  # the copy behind the fold, on the stream that ran it
+            k, s, b = self._totals.tolist()
+        return {"skipped": k, "solved": s, "budget": b}
+
+    def reset_counts(self):
+        self._fold()
+        with torch.cuda.stream(self.engine.stream):
+            self._totals.zero_()
+
+    @property
+    def solved(self):
+        return self.counts()["solved"]
+
+    @property
+    def budget(self):
+        return self.counts()["budget"]
+
+    @property
+    def skipped(self):
+        return self.counts()["skipped"]
+
+
 class NetworkEvaluator:
     """DualNetwork (or any model with its call signature) on the engine's device."""
 

@@ -13,6 +13,8 @@ from ._lib import STATE_DTYPE, UtttState, check, ptr
 from .engine import as_states
 
 SOLVED, BUDGET, TOO_LARGE = 1, 2, 3  # UTTT_SOLVE_*
+SKIPPED = 0                          # UTTT_OVERLAY_SKIPPED: the overlay did not search the position
+PRIORS_KEEP, PRIORS_OPTIMAL = 0, 1   # UTTT_PRIORS_*
 UNKNOWN = -128                       # UTTT_SOLVE_UNKNOWN: an unsolved or illegal action's value
 MAX_EMPTY = 32                       # UTTT_SOLVE_MAX_EMPTY: the deepest position searched
 
@@ -39,6 +41,37 @@ def solve_with(call, states, max_nodes):
 def solve_host(states, max_nodes=65536):
     """Engine.solve on the CPU (uttt_solve_host): needs no GPU."""
     return solve_with(_lib.load().uttt_solve_host, states, max_nodes)
+
+
+def priors_mode(priors):
+    """UTTT_PRIORS_* of "keep" / "optimal" (or of the number itself)."""
+    if isinstance(priors, str):
+        if priors not in ("keep", "optimal"):
+            raise ValueError(f'priors must be "keep" or "optimal" (got {priors!r})')
+        return PRIORS_OPTIMAL if priors == "optimal" else PRIORS_KEEP
+    return int(priors)
+
+
+def overlay_host(states, policy, value, max_empties, max_nodes, priors):
+    """Engine.eval_solve_dev on the CPU (uttt_solve_overlay_host): lays the exact values of `states` over the
+    rows policy ((n, >=81) float32, unit stride along the actions) and value ((n,) or (n, 1) float32) in place
+    and returns the int8 status per row (SKIPPED / SOLVED / BUDGET)."""
+    st = as_states(states)
+    n = len(st)
+    ok = (isinstance(policy, np.ndarray) and isinstance(value, np.ndarray) and policy.dtype == np.float32
+          and value.dtype == np.float32 and policy.ndim == 2 and len(policy) == n and value.shape in ((n,), (n, 1)))
+    if not ok or (n and (policy.strides[1] != 4 or policy.strides[0] % 4 or value.strides[0] % 4)):
+        raise ValueError("overlay_host: policy (n, >=81) and value (n,) or (n, 1), float32 numpy rows")
+    if policy.shape[1] < 81:
+        raise ValueError("overlay_host: a policy row has 81 entries")
+    if not (policy.flags.writeable and value.flags.writeable):
+        raise ValueError("overlay_host: the rows are updated in place")
+    status = np.zeros(n, np.int8)
+    check(_lib.load().uttt_solve_overlay_host(
+        st.ctypes.data_as(ctypes.POINTER(UtttState)), n, int(max_empties), int(max_nodes), priors_mode(priors),
+        ptr(policy, ctypes.c_float), policy.strides[0] // 4 if n else 81, ptr(value, ctypes.c_float),
+        value.strides[0] // 4 if n else 1, ptr(status, ctypes.c_int8)))
+    return status
 
 
 def empties(states):
