@@ -10,7 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-WAVES_PER_BLOCK = 4  # engine.hip kWavesPerBlock: one wave per position
+WAVES_PER_BLOCK = 4  # csrc/engine/layout.h kWavesPerBlock: one wave per position
 P_SEARCH, SEED = 8, 0xC0FFEE
 
 

@@ -9,7 +9,7 @@ from test_solve_host import (BUDGET, MAX_EMPTY, SOLVED, TOO_LARGE, board2_positi
 
 pytestmark = pytest.mark.gpu
 
-WAVES_PER_BLOCK = 4  # engine.hip kWavesPerBlock: one wave per position
+WAVES_PER_BLOCK = 4  # csrc/engine/layout.h kWavesPerBlock: one wave per position
 NAMES = ("value", "action", "status", "nodes", "action_values")
 
 

@@ -13,7 +13,7 @@ from test_solve_host import empties_py, late_positions
 
 pytestmark = pytest.mark.gpu
 
-WAVES_PER_BLOCK = 4  # engine.hip kWavesPerBlock: one wave per leaf
+WAVES_PER_BLOCK = 4  # csrc/engine/layout.h kWavesPerBlock: one wave per leaf
 N_TAIL = 4 * WAVES_PER_BLOCK + 1
 SKIPPED, SOLVED, BUDGET = 0, 1, 2
 P_SEARCH, SEED = 8, 0xC0FFEE

@@ -20,6 +20,12 @@
 // Self-play (self_play_cpp.py) adds k_move_end (scores, f64 policy target,
 // numpy-legacy MT19937 choice, records), k_finalize (refill + arena offsets)
 // and k_archive.
+//
+// One translation unit. What every kernel below builds on lives in engine/, included here in this order:
+//   layout.h  errors, HIP_TRY, constants, KernelId, TreeCtl / LeafRec / HostLeaf / Pool / Trees, node records
+//   wave.h    lane / wave helpers, DPP arg-max, host-visible stores
+//   cache.h   EvalCache: probe, lookup, insert
+//   expand.h  legal masks, f32 sums, expand_backup, init_root, k_begin
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -37,723 +43,12 @@
 #include "uttt_playout.h"
 #include "uttt_solve.h"
 
+#include "engine/layout.h"
+#include "engine/wave.h"
+#include "engine/cache.h"
+#include "engine/expand.h"
+
 namespace uttt {
-
-// ------------------------------------------------------------------ errors --
-void set_error(const char *fmt, ...);  // rules_api.cpp (uttt_last_error)
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return UTTT_ERR_HIP;                                                             \
-        }                                                                                    \
-    } while (0)
-
-// ------------------------------------------------------------------ layout --
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
-constexpr int kMaxDepth = 128;  // path slots: lane d holds path[d] and path[64 + d]
-constexpr int kMaxPlies = 81;   // a game fills at most every cell
-constexpr int kNone = 0x7fffffff;
-
-constexpr int32_t kLive = 1;
-constexpr int32_t kErrCapacity = 2;
-constexpr int32_t kErrDepth = 4;
-constexpr int32_t kErrSelect = 8;
-constexpr int32_t kErrNonFinite = 16;  // the evaluator returned a NaN / Inf legal prior or value
-constexpr int32_t kErrMask = kErrCapacity | kErrDepth | kErrSelect | kErrNonFinite;
-
-// a failed tree's status -> message and UTTT_ERR_* (the checks that raise it are at the move / search end)
-static const char *tree_error_text(uint32_t st) {
-    return (st & kErrCapacity)    ? "node pool exhausted"
-           : (st & kErrDepth)     ? "path deeper than 128"
-           : (st & kErrNonFinite) ? "non-finite evaluator output (NaN or Inf in a legal prior or the value)"
-                                  : "no selectable child (NaN statistics)";
-}
-static int tree_error_code(uint32_t st) {
-    return (st & kErrCapacity) || (st & kErrDepth) ? UTTT_ERR_CAPACITY
-           : (st & kErrNonFinite)                  ? UTTT_ERR_NONFINITE
-                                                   : UTTT_ERR_ARG;
-}
-
-enum KernelId {
-    kKSelect = 0, kKApply, kKEncode, kKScan, kKMoveEnd, kKHash,
-    // select latency telemetry (counters only, no launches): dependent tree levels walked
-    // (sum over trees of sum over descents of depth + 1), trees that descended, the current
-    // launch's slowest tree (folded into the sum by k_scan after every select), that sum
-    kKSelLevels, kKSelTrees, kKSelMax, kKSelMaxSum,
-    // dependent memory round trips (the latency model's unit): sum over trees, the current launch's
-    // slowest tree, that slowest count summed over launches
-    kKSelTrips, kKSelTripMax, kKSelTripMaxSum,
-    // the slowest-tree rows of odd rounds in uttt_rounds_hash_move's per-block form (k_round1 with part_host):
-    // each round folds the previous round's rows at its start, so no round needs a last block
-    kKSelMaxB, kKSelTripMaxB,
-    kKPlayout,  // k_playout_leaves / k_playout_states launches
-    kKSolve,    // k_solve_states launches
-    kKSolveLeaves,  // k_solve_leaves launches
-    kKernelCount
-};
-static_assert(kKSolveLeaves == 17, "the public header and _lib.KERNELS state the ids");
-
-// Device counters are striped: counter i of a row lives in kStripes 128-byte slots, and a workgroup
-// adds into slot (blockIdx & (kStripes - 1)), so thousands of waves finishing together do not
-// serialize on one address (the host sums the slots).
-constexpr int kStripes = 32;
-constexpr int kStripeStride = 16;  // u64 per slot: 128 B
-constexpr int kRow = kStripes * kStripeStride;  // u64 per counter
-__device__ __forceinline__ unsigned long long *stripe_of(unsigned long long *row) {
-    return row + (size_t)(blockIdx.x & (kStripes - 1)) * kStripeStride;
-}
-
-struct TreeCtl {
-    int32_t sims_done;
-    int32_t node_count;
-    int32_t status;
-    int32_t pad;
-};
-
-struct LeafRec {
-    int32_t node;
-    int32_t depth;
-    int32_t k;
-    int32_t pad;
-};
-
-// A single-tree search's round result in fine-grained pinned host memory (round 5, uttt_search_select_host):
-// k_scan stores the counts, the pending leaf's state and its copies, then the tag (a system-scope release),
-// and the host polls the tag: one select per flush costs no copy operation and no stream synchronisation
-// (the reference's flush loop, uttt_mcts.cpp:109-167, runs in-process).
-struct HostLeaf {
-    int32_t count, stopped, left, tag;
-    int32_t k, pad0, pad1, pad2;
-    uttt_state_t state;
-};
-
-// One node (round 4: four SoA arrays N, W, P, LINK became one record, so the PUCT scan loads a child
-// with one dwordx4 and an expansion stores a child with one):
-//   .x W (f32 bits)   .y P (f32 bits)
-//   .z meta: visits N (bits 0-15) | action (16-22) | L = |legal| of the node's state, the size of
-//      each of its child blocks (23-29) | kMetaP64 (30) | kMetaWF32 (31)
-//   .w link: first child (bits 0-19) | k = its child blocks (20-31)
-// Limits: max_sims <= 4095 (k and N fit; the pool cap 82 + 81 * max_sims < 2^20 first-child indices).
-struct Pool {
-    uint4 *rec;
-    int64_t cap;
-};
-constexpr int kMaxSimsRec = UTTT_MAX_SIMS;
-static_assert(82 + 81ll * kMaxSimsRec < (1ll << 20), "first-child index: 20 bits");
-constexpr int kCountRing = 8;  // host-visible count slots per engine (uttt_search_select_async_tag, uttt_round_hash_async)
-
-struct Trees {
-    TreeCtl *ctl;
-    uttt_state_t *root;
-    uttt_state_t *leaf;
-    LeafRec *rec;
-    int32_t *path;    // [tree][kMaxDepth]
-    uint4 *path_rec;  // [tree][kMaxDepth]: the path nodes' records as the select read them (k_apply's back-up
-                      // starts from them instead of re-reading each node: one dependent round trip less)
-    int32_t *pending; // [tree]: 0 nothing, 2 stopped by the select budget, 1 / 3 a queued leaf (3: the
-                      // tree has simulations left after it) | the leaf's depth << 8
-    int32_t *tree_of; // [slot]
-    int32_t *depth_of; // [slot]: the queued leaf's depth (k_apply loads only the path entries it uses)
-    int32_t *count;   // [0] pending leaves this round, [1] trees stopped by the select budget,
-                      // [2] trees with simulations left after this round's apply
-    int32_t n_trees;
-    int32_t sims;
-    int32_t batch;
-    int32_t py;  // 1: pv_mcts.py semantics (arena), 0: cpp/uttt_mcts.cpp (self-play)
-    int32_t budget;  // in-place completions per tree and select launch (kSelectBudget; UTTT_SELECT_BUDGET)
-};
-// count[3]: nonzero once any tree of the search has failed (reset by k_begin): the asynchronous move end reads
-// it instead of a launch that scans every tree's status (k_finalize finds the first failed tree only then)
-__device__ __forceinline__ void flag_tree_error(const Trees &tr) { atomicOr(tr.count + 3, 1); }
-
-// record packing (Pool)
-constexpr uint32_t kNoAction = 0x7Fu;
-__host__ __device__ __forceinline__ uint32_t make_meta(uint32_t action, uint32_t L) {  // N = 0
-    return ((action & 0x7Fu) << 16) | ((L & 0x7Fu) << 23);
-}
-__host__ __device__ __forceinline__ int meta_n(uint32_t m) { return (int)(m & 0xFFFFu); }
-__host__ __device__ __forceinline__ int meta_action(uint32_t m) { return (int)((m >> 16) & 0x7Fu); }
-__host__ __device__ __forceinline__ int meta_L(uint32_t m) { return (int)((m >> 23) & 0x7Fu); }
-// py semantics only (pv_mcts.py, NumPy 2 scalar promotion):
-constexpr uint32_t kMetaP64 = 1u << 30;   // this node's children carry float64 uniform priors
-constexpr uint32_t kMetaWF32 = 1u << 31;  // this node's w has become np.float32 (a network value)
-constexpr uint32_t kMetaLMask = 0x7Fu << 23;
-__host__ __device__ __forceinline__ uint32_t make_link(uint32_t first, uint32_t k) { return (first & 0xFFFFFu) | (k << 20); }
-__host__ __device__ __forceinline__ int link_first(uint32_t l) { return (int)(l & 0xFFFFFu); }
-__host__ __device__ __forceinline__ int link_k(uint32_t l) { return (int)(l >> 20); }
-__device__ __forceinline__ uint4 new_child(float p, uint32_t action) {
-    return make_uint4(0u, __float_as_uint(p), make_meta(action, 0u), 0u);
-}
-
-// ------------------------------------------------------------ wave helpers --
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (kWave - 1)); }
-// This wave's global index (one wave per tree / slot / row), marked wave-uniform: what is derived from
-// it (the tree's control words, its states, the rules applied to them) lives in scalar registers and
-// runs on the scalar unit instead of as 64 identical vector lanes (round 4)
-__device__ __forceinline__ int wave_index() {
-    return __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)));
-}
-
-__device__ __forceinline__ uint64_t lanes_below() {
-    const int l = lane_id();
-    return l == 0 ? 0ull : (~0ull >> (64 - l));
-}
-
-// Wave-wide arg-max: larger value wins, equal values -> smaller index
-// (the reference's strict '>' scan in child order, uttt_mcts.cpp:69-78).
-__device__ __forceinline__ void wave_argmax_d(double &v, int &i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
-__device__ __forceinline__ float readlane_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
-// The same arg-max by DPP lane moves, no LDS round trips (k_select's per-level reduction): the wave's
-// largest value by one reduction of one instruction pair per step, then the smallest index among the
-// lanes holding it ("larger value, then smaller index": the reference's strict '>' scan in child order)
-// from one ballot when the maximum is unique, else from per-group ballots. Values are never NaN here (the per-lane scan's strict '>' from -1e9 never takes one); -0 and
-// +0 compare equal, so they tie on the index as in the scan. Each reduction runs within each row of 16
-// lanes (quad swaps, half-row and row mirrors), then row 0 into row 1 and row 2 into row 3
-// (row_bcast15), then row 1 into rows 2-3 (row_bcast31): the result is valid in lane 63.
-// one reduction step as a single DPP-sourced VALU op (the two wait states a DPP read of a VGPR
-// written by the previous VALU op needs are in the asm: the compiler does not see inside it)
-#define UTTT_DPP_STEP(op, ctl)                                                                     \
-    __device__ __forceinline__ void op##_##ctl(uint32_t &k) {                                      \
-        asm volatile("s_nop 1\n\t" #op "_dpp %0, %0, %0 " UTTT_DPP_##ctl : "+v"(k));             \
-    }
-#define UTTT_DPP_q1 "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-#define UTTT_DPP_q2 "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-#define UTTT_DPP_hm "row_half_mirror row_mask:0xf bank_mask:0xf"
-#define UTTT_DPP_rm "row_mirror row_mask:0xf bank_mask:0xf"
-#define UTTT_DPP_b15 "row_bcast:15 row_mask:0xa bank_mask:0xf"
-#define UTTT_DPP_b31 "row_bcast:31 row_mask:0xc bank_mask:0xf"
-UTTT_DPP_STEP(v_max_u32, q1)
-UTTT_DPP_STEP(v_max_u32, q2)
-UTTT_DPP_STEP(v_max_u32, hm)
-UTTT_DPP_STEP(v_max_u32, rm)
-UTTT_DPP_STEP(v_max_u32, b15)
-UTTT_DPP_STEP(v_max_u32, b31)
-// wave-uniform result: the index of the largest v, the lowest index among equal maxima
-// (cnt: the scanned child count; candidate indices are below it)
-__device__ __forceinline__ int wave_argmax(float v, int i, int cnt) {
-    // the value as an order-preserving unsigned (-0 canonicalised to +0 first), so each step of the max
-    // is an integer max (no float canonicalisation)
-    uint32_t b = __float_as_uint(v + 0.0f);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    uint32_t m = b;
-    v_max_u32_q1(m);   // quad_perm [1,0,3,2]
-    v_max_u32_q2(m);   // quad_perm [2,3,0,1]
-    v_max_u32_hm(m);   // row_half_mirror
-    v_max_u32_rm(m);   // row_mirror
-    v_max_u32_b15(m);  // row_bcast15 -> rows 1, 3
-    v_max_u32_b31(m);  // row_bcast31 -> rows 2, 3
-    asm volatile("s_nop 1");  // the asm's VALU write before the compiler's reads of m
-    const uint32_t top = (uint32_t)__builtin_amdgcn_readlane((int)m, 63);
-    // the usual case: one lane holds the maximum, and its index is the answer (no second pass)
-    const uint64_t at = __ballot(b == top);
-    if (__popcll(at) == 1) return __builtin_amdgcn_readlane(i, __builtin_ctzll(at));
-    // ties (a node expanded by a flush of k copies holds k equal children per action until they are
-    // visited): the smallest index among the lanes holding the maximum. Lane l's candidate is its own first
-    // maximum, child l + 64 g of its scan group g (i & 63 == l), so the answer is the lowest such lane of
-    // the lowest group present: one ballot per group from group 0 (round 5: in place of a second 6-step DPP
-    // reduction and its wait states; usually group 0 or 1 answers). Every scan group of the node is
-    // covered: a flush of k copies gives up to k x 81 children, more than 64 groups past batch 50.
-    const int ngroups = (cnt + kWave - 1) / kWave;
-    for (int g = 0; g < ngroups; ++g) {
-        const uint64_t m = __ballot(b == top && (i >> 6) == g);
-        if (m) return g * kWave + __builtin_ctzll(m);
-    }
-    return kNone;  // unreachable: some lane holds the maximum with a child index
-}
-
-// Orders this wave's global stores before its later global loads (other lanes
-// read what one lane wrote; same CU, so workgroup scope suffices).
-__device__ __forceinline__ void wave_memory_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-
-// Stores to host-visible (fine-grained pinned) words: system-coherent (sc0 sc1) and relaxed. A hand-off to
-// the host is these stores, one s_waitcnt vmcnt(0) (they are acknowledged), then the tag, also relaxed: no
-// release fence, whose L2 write-back (buffer_wbl2 sc0 sc1) would flush every line the kernel dirtied in the
-// XCD's L2 (tree records, rows) to HBM at each hand-off, when the host reads only these words (round 6)
-__device__ __forceinline__ void st_host(int32_t *a, int32_t v) {
-    __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void st_host(float *a, float v) {
-    __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void host_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// ------------------------------------------------------ evaluation cache --
-// Open-addressing table in HBM: position (32 B) -> raw evaluator output (81
-// priors + value, before legal masking). The evaluator is a pure function of
-// the position (the reference feeds it to_input_tensor(), uttt_game.cpp:244),
-// so a hit replays exactly what a new evaluation would return. Looked up in
-// k_select (a hit is expanded in place: no network round), filled by k_apply.
-constexpr int kProbe = 8;
-constexpr int kCacheVal = 82;
-// One record per slot, three 128-byte lines: the key (32 B), the 82 values (328 B), padding. Written
-// and read as 16-byte agent-scope (sc1) accesses, 23 lanes of one wave: one fabric write per 16 B
-// instead of one per 4-byte store (MI355X_MICROARCH.md: narrow sc1 stores are one fabric write each).
-constexpr int kRecBytes = 384;
-constexpr int kRecVal = 32;  // the key is the record's first 32 bytes
-constexpr int kRecLanes = 23;  // 16-byte pieces written per record: 2 of key, 21 of values
-constexpr int kSc1 = 16;       // buffer-intrinsic cache-policy bit: sc1 (agent scope)
-static_assert(kRecVal + 16 * (kRecLanes - 2) >= kRecVal + 4 * kCacheVal && 16 * kRecLanes <= kRecBytes, "record");
-
-struct EvalCache {
-    // Per slot one flag word: bits 0-15 a version (0 empty; odd: a writer holds the slot; even >= 2:
-    // ready), bits 16-31 the ready entry's tag (16 bits of its position's hash). A writer claims by
-    // CAS from the value it saw to that + 1 and publishes the version + 2 with the new tag, so every
-    // publish is a new flag value: a reader compares the flag it probed with the flag after its copy
-    // (a seqlock without ABA). Probes read only the flags (32 contiguous bytes for 8 slots) and
-    // load a record only for a ready slot whose tag matches (round 4: rounds 1-3 read 8 keys per probe).
-    uint32_t *flag;
-    char *rec;           // [slot][kRecBytes]
-    uint32_t mask;       // capacity - 1
-    unsigned long long *ctr;  // [0] hits, [1] misses (network leaves), [2] inserts, [3] replacements
-};
-
-__device__ __forceinline__ bool flag_ready(uint32_t f) { return (f & 0xFFFFu) != 0u && !(f & 1u); }
-__device__ __forceinline__ uint32_t flag_tag(uint32_t f) { return f >> 16; }
-// the flag that publishes a slot claimed from flag f (f & 0xFFFF even, or 0 for an empty slot)
-__device__ __forceinline__ uint32_t flag_publish(uint32_t f, uint32_t tag) {
-    const uint32_t v = (f & 0xFFFFu) + 2u;
-    return (tag << 16) | (v > 0xFFFFu ? 2u : v);
-}
-
-__device__ __forceinline__ uint64_t state_hash64(const uttt_state_t &s) {
-    const uint64_t a = ((uint64_t)s.own[1] << 32) | s.own[0];
-    const uint64_t b = ((uint64_t)s.opp[0] << 32) | s.own[2];
-    const uint64_t c = ((uint64_t)s.opp[2] << 32) | s.opp[1];
-    const uint64_t d = ((uint64_t)(uint32_t)s.active << 32) | s.mains;
-    return mix64(mix64(mix64(mix64(kGold ^ a) ^ b) ^ c) ^ d);
-}
-// a position's tag: the top 16 bits of its hash (its slot: the low 32 bits)
-__device__ __forceinline__ uint32_t state_tag(uint64_t h64) { return (uint32_t)(h64 >> 48); }
-
-// 16-byte piece `hi` (0 or 1) of a position's 32-byte key, by selects: indexing the state's words by a
-// lane-dependent offset made the state a private array, which the compiler placed in LDS addressed by
-// the flat work-item id, i.e. a read of the dispatch packet in host memory at every launch (round 4:
-// 2-26 us before k_select's first descent, tools/diag/select_cycles.py)
-__device__ __forceinline__ uint4 key_piece(const uttt_state_t &s, bool hi) {
-    return make_uint4(hi ? s.opp[1] : s.own[0], hi ? s.opp[2] : s.own[1], hi ? s.mains : s.own[2],
-                      hi ? (uint32_t)s.active : s.opp[0]);
-}
-
-__device__ __forceinline__ bool same_state(const uttt_state_t &x, const uttt_state_t &y) {
-    return x.own[0] == y.own[0] && x.own[1] == y.own[1] && x.own[2] == y.own[2] && x.opp[0] == y.opp[0] &&
-           x.opp[1] == y.opp[1] && x.opp[2] == y.opp[2] && x.mains == y.mains && x.active == y.active;
-}
-
-// The table may be shared by several engines whose kernels run concurrently on
-// other XCDs, whose L2s are not coherent with this one: every access to flag and
-// record is agent-scope (sc1: relaxed agent atomics, or buffer accesses with the
-// sc1 bit). Entries are exact (the evaluator is a pure function of the position),
-// so any ready entry with a matching key is correct; a reader re-checks the flag
-// after copying the values, so an entry rewritten meanwhile is never mixed into the copy.
-template <typename T>
-__device__ __forceinline__ T ld_agent(const T *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ void st_agent(T *p, T v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-// a wave-uniform slot's record as a 384-byte buffer
-__device__ __forceinline__ rsrc_t rec_rsrc(const EvalCache &c, uint32_t slot) {
-    slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
-    return __builtin_amdgcn_make_buffer_rsrc(c.rec + (size_t)slot * kRecBytes, 0, kRecBytes, 0x00020000);
-}
-
-// Wave-uniform lookup: lanes 0..kProbe-1 read the kProbe slots' flags at once; the first ready slot
-// whose tag matches (a hit counts only if no empty slot precedes it in probe order) has its whole
-// record read in one round trip (lanes 0-1 the key, checked against s; 2-22 the values), then the
-// flag is re-checked. On a hit the 82 values are copied to dst (LDS, 16-byte aligned, >= 84 floats)
-// and true is returned; a tag that matched another position's entry (a 16-bit collision) is a miss.
-// The probe in two halves: the flags' loads are issued first, so work that does not need them (the select's
-// leaf checks) runs under their round trip (round 6)
-struct CacheProbe {
-    uint64_t h64;
-    uint32_t f;  // lane l < kProbe: flag of slot h + l
-};
-__device__ __forceinline__ CacheProbe cache_probe_issue(const EvalCache &c, const uttt_state_t &s) {
-    CacheProbe p;
-    p.h64 = 0ull;
-    p.f = 0u;
-    if (!c.flag) return p;
-    const int lane = (int)(threadIdx.x & 63);
-    p.h64 = state_hash64(s);
-    p.f = lane < kProbe ? ld_agent(c.flag + (((uint32_t)p.h64 + (uint32_t)lane) & c.mask)) : 0u;
-    return p;
-}
-
-__device__ bool cache_lookup_probed(const EvalCache &c, const CacheProbe &pr, const uttt_state_t &s, float *dst) {
-    if (!c.flag) return false;
-    const int lane = (int)(threadIdx.x & 63);
-    const uint64_t h64 = pr.h64;
-    const uint32_t h = (uint32_t)h64, tag = state_tag(h64);
-    const uint32_t f = pr.f;
-    const uint64_t cand = __ballot(lane < kProbe && flag_ready(f) && flag_tag(f) == tag);
-    const uint64_t empty = __ballot(lane < kProbe && f == 0u);
-    if (!cand) return false;
-    const int hl = __builtin_ctzll(cand);
-    if (empty && __builtin_ctzll(empty) < hl) return false;
-    const uint32_t hs = (h + (uint32_t)hl) & c.mask;
-    const uint32_t f1 = (uint32_t)__builtin_amdgcn_readlane((int)f, hl);
-    const rsrc_t r = rec_rsrc(c, hs);
-    u32x4_t piece = {0u, 0u, 0u, 0u};
-    if (lane < kRecLanes) piece = __builtin_amdgcn_raw_buffer_load_b128(r, 16 * lane, 0, kSc1);
-    // seqlock read side: the record loads are served before the re-check is issued; any writer
-    // that touched the record since the probe bumped the flag first (claim), so the re-check differs
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint4 kp = key_piece(s, (lane & 1) != 0);
-    const bool key_ok = piece[0] == kp.x && piece[1] == kp.y && piece[2] == kp.z && piece[3] == kp.w;
-    if (__ballot(lane < 2 && !key_ok)) return false;
-    bool ok = true;
-    if (lane == 0) ok = ld_agent(c.flag + hs) == f1;
-    if (!__shfl(ok, 0)) return false;
-    if (lane >= 2 && lane < kRecLanes) *reinterpret_cast<u32x4_t *>(dst + 4 * (lane - 2)) = piece;
-    return true;
-}
-
-// Wave-level insert of (s -> 81 priors, value): lane l holds prior l in p0 and prior 64 + l in p1
-// (l < 17). Lane 0 claims a slot by CAS (flag -> odd); the record is stored as 23 16-byte sc1
-// pieces and drained (s_waitcnt vmcnt(0)) before the new flag is published, so a reader on
-// any XCD that sees the flag sees the data. A ready slot with this position's tag counts as this
-// position (no insert; a 16-bit collision only costs a missed entry), and a concurrent insert of
-// the same key may leave a harmless duplicate. When all kProbe slots hold other positions, one of
-// them (chosen by the hash) is replaced. Entries are exact, so the table never needs clearing
-// while the evaluator is unchanged: it stays warm across moves. Returns whether a record was written.
-// sum >= 0 marks `psum` (the sequential f32 sum of the legal priors, uttt_mcts.cpp:150-153, as
-// expand_backup computed it) valid: it is stored beside the values (value 82, with 1.0f at 83), so a
-// hit expands without re-adding up to 81 priors one dependent add after another.
-constexpr int kRecSum = 82, kRecSumFlag = 83;
-// A publish held back by cache_insert (defer): the claimed slot and its flag value, stored by the caller once
-// its own later stores are drained anyway (k_round1's end of block), so the record's drain is not a round
-// trip of its own on the wave's chain (round 6)
-struct CachePublish {
-    int32_t slot;  // -1: nothing held
-    uint32_t pub;
-};
-__device__ __forceinline__ void cache_publish(const EvalCache &c, const CachePublish &d) {
-    if (d.slot < 0 || (threadIdx.x & 63) != 0) return;
-    st_agent(c.flag + d.slot, d.pub);
-    atomicAdd(stripe_of(c.ctr + 2 * kRow), 1ull);
-}
-
-// pr: the kProbe slots' flags for s, loaded ahead (cache_probe_issue, before the expansion's work)
-__device__ bool cache_insert(const EvalCache &c, const CacheProbe &pr, const uttt_state_t &s, float p0, float p1, float v,
-                             bool has_sum = false, float psum = 0.0f, CachePublish *defer = nullptr) {
-    if (!c.flag) return false;
-    const int lane = (int)(threadIdx.x & 63);
-    int slot = -1;
-    uint32_t pub = 0u;
-    // the kProbe slots' flags in one round trip (lanes 0..kProbe-1), then lane 0 acts on the first
-    // slot that holds this position's tag or is empty; a lost claim falls back to probing one slot
-    // after another from there
-    const uint64_t h64 = pr.h64;
-    const uint32_t h = (uint32_t)h64, tag = state_tag(h64);
-    const uint32_t f = pr.f;
-    const uint64_t here = __ballot(lane < kProbe && flag_ready(f) && flag_tag(f) == tag);
-    const uint64_t free_ = __ballot(lane < kProbe && f == 0u);
-    const uint64_t either = here | free_;
-    const int first = either ? __builtin_ctzll(either) : kProbe;
-    if (lane == 0) {
-        bool present = first < kProbe && ((here >> first) & 1ull);
-        int i0 = first;
-        if (!present && first < kProbe) {
-            const uint32_t sl = (h + (uint32_t)first) & c.mask;
-            if (atomicCAS(c.flag + sl, 0u, 1u) == 0u) {
-                slot = (int)sl;
-                pub = flag_publish(0u, tag);
-            } else {
-                i0 = first + 1;
-            }
-        }
-        for (int i = i0; slot < 0 && !present && i < kProbe; ++i) {
-            const uint32_t sl = (h + (uint32_t)i) & c.mask;
-            const uint32_t fi = ld_agent(c.flag + sl);
-            if (flag_ready(fi) && flag_tag(fi) == tag) {
-                present = true;
-                break;
-            }
-            if (fi == 0u && atomicCAS(c.flag + sl, 0u, 1u) == 0u) {
-                slot = (int)sl;
-                pub = flag_publish(0u, tag);
-                break;
-            }
-        }
-        if (slot < 0 && !present) {  // every probe slot taken: replace one (version v -> v + 1 -> v + 2)
-            const uint32_t sl = (h + (h >> 29)) & c.mask;
-            const uint32_t fr = ld_agent(c.flag + sl);
-            if (flag_ready(fr) && atomicCAS(c.flag + sl, fr, fr + 1u) == fr) {
-                slot = (int)sl;
-                pub = flag_publish(fr, tag);
-                atomicAdd(stripe_of(c.ctr + 3 * kRow), 1ull);
-            }
-        }
-    }
-    slot = __shfl(slot, 0);
-    if (slot < 0) return false;
-    pub = (uint32_t)__builtin_amdgcn_readfirstlane((int)pub);
-    // piece j of the record: j < 2 the key's words 4j..4j+3, else values 4(j-2)..4(j-2)+3
-    // (value e < 64: lane e's p0; e < 81: lane e-64's p1; e == 81: v)
-    floatx4_t piece;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = 4 * (lane - 2) + i;
-        const float a = __shfl(p0, e & 63);
-        const float b = __shfl(p1, (e - 64) & 63);
-        piece[i] = e < 64 ? a
-                          : (e < 81 ? b
-                                    : (e == 81 ? v : (e == kRecSum && has_sum ? psum : (e == kRecSumFlag && has_sum ? 1.0f : 0.0f))));
-    }
-    if (lane < 2) {
-        const uint4 kp = key_piece(s, lane != 0);
-        piece = floatx4_t{__uint_as_float(kp.x), __uint_as_float(kp.y), __uint_as_float(kp.z), __uint_as_float(kp.w)};
-    }
-    const rsrc_t r = rec_rsrc(c, (uint32_t)slot);
-    // all 24 pieces (the padding as zeros): the record's three 128-byte lines are written whole, so none is
-    // a partial-line write at the memory side (round 6; 23 pieces left the third line 112 of 128 bytes)
-    if (lane < kRecBytes / 16)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, piece), r, 16 * lane, 0, kSc1);
-    if (defer) {  // the caller drains and publishes
-        defer->slot = slot;
-        defer->pub = pub;
-        return true;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    cache_publish(c, CachePublish{slot, pub});
-    return true;
-}
-
-// ---------------------------------------------------------- expand + backup --
-// uttt_mcts.cpp:138-167 for k identical copies of one flushed leaf: priors =
-// pol[a] for legal a, sequential f32 sum in action order, divide (uniform
-// 1/|legal| if the sum is <= 0); append k child blocks (expand never clears,
-// :38-43); back up v k times along path[0..depth] (:47-54, leaf first, sign
-// flipping upward). Lane d holds path[d] in path_lo and path[64+d] in path_hi.
-// Returns false without writing when the node pool would overflow.
-// py (pv_mcts.py:46-56, :104-116): priors normalised by np.sum (float32 pairwise),
-// all-zero -> float64 uniform (kMetaP64); ONE child block (expand replaces, and
-// the k copies of a flush expand the same children); every node on the path
-// gets a network value, so its w becomes float32 (kMetaWF32).
-
-// A state's legal moves compacted over the wave: lane l holds action l (l0) and action 64 + l (l1, l < 17);
-// b0 / b1 their ballots, L = |legal|, i0 / i1 this lane's actions' ranks in action order. on == false
-// (k_begin's dead slots): no move counts as legal.
-struct Legal {
-    bool l0, l1;
-    uint64_t b0, b1;
-    int L, i0, i1;
-};
-__device__ __forceinline__ Legal legal_of(const uttt_state_t &s, bool on = true) {
-    const int lane = lane_id();
-    uint32_t m[3];
-    legal_mask(s, m);
-    Legal g;
-    g.l0 = on && bit_of(m, lane) != 0u;
-    g.l1 = on && lane < 17 && bit_of(m, 64 + lane) != 0u;
-    g.b0 = __ballot(g.l0);
-    g.b1 = __ballot(g.l1);
-    g.L = __popcll(g.b0) + __popcll(g.b1);
-    g.i0 = __popcll(g.b0 & lanes_below());
-    g.i1 = __popcll(g.b0) + __popcll(g.b1 & lanes_below());
-    return g;
-}
-
-__device__ float np_sum_f32_legal(float p0, float p1, uint64_t b0, uint64_t b1, int L) {
-    // numpy pairwise_sum for float32, n <= 128: 8 strided accumulators, then the tail
-    auto nth = [&](int idx) -> float {  // idx-th legal prior in action order (wave-uniform)
-        const int c0 = __popcll(b0);
-        uint64_t bits = idx < c0 ? b0 : b1;
-        int r = idx < c0 ? idx : idx - c0;
-        for (; r > 0; --r) bits &= bits - 1ull;
-        const int l = __builtin_ctzll(bits);
-        return idx < c0 ? readlane_f(p0, l) : readlane_f(p1, l);
-    };
-    if (L < 8) {
-        float res = 0.0f;
-        for (int i = 0; i < L; ++i) res += nth(i);
-        return res;
-    }
-    float r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = nth(j);
-    const int main_end = L - L % 8;
-    for (int i = 8; i < main_end; i += 8)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += nth(i + j);
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (int i = main_end; i < L; ++i) res += nth(i);
-    return res;
-}
-
-// raw0 / raw1: this lane's prior of action lane / 64 + lane (lane < 17), loaded by the caller
-// The sequential f32 sum of the legal priors in action order (uttt_mcts.cpp:150-153): each legal
-// prior is stored at its rank in the wave's LDS row (zeros pad the row to a multiple of 4; adding
-// +0.0 to a sum that started at +0.0 changes nothing), then every lane reads the row back by
-// broadcast 16-byte reads and adds it up in order: one dependent add per prior, instead of a scalar
-// find-first-bit, a v_readlane and an add per prior.
-__device__ __forceinline__ void store_ranked_row(float *row /* LDS, 16-B aligned, >= 84 floats */, float p0, float p1,
-                                                 const Legal &g) {
-    const int lane = lane_id();
-    if (g.l0) row[g.i0] = p0;
-    if (g.l1) row[g.i1] = p1;
-    // L4 - L < 4 <= 64: lanes L .. L4-1 pad (first item: no lane pads a row of 65-83 legal moves)
-    if (lane >= g.L && lane < ((g.L + 3) & ~3)) row[lane] = 0.0f;
-}
-__device__ __forceinline__ float sum_row4(const float *row, int L) {
-    // the other lanes' stores before any lane's reads (LDS executes a wave's accesses in order; the
-    // wait and the clobber keep the compiler from hoisting the reads above the stores)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float sum = 0.0f;
-    const float4 *r4 = reinterpret_cast<const float4 *>(row);
-    for (int i = 0; i < ((L + 3) & ~3) / 4; ++i) {
-        const float4 q = r4[i];
-        sum += q.x;
-        sum += q.y;
-        sum += q.z;
-        sum += q.w;
-    }
-    return sum;
-}
-__device__ __forceinline__ float seq_sum_legal(float *row, float p0, float p1, const Legal &g) {
-    store_ranked_row(row, p0, p1, g);
-    return sum_row4(row, g.L);
-}
-
-// rec_lo / rec_hi: this lane's path node's record (path[lane] / path[64 + lane]) as the select read it
-__device__ bool expand_backup(const Pool &pool, size_t base, int node, int depth, int path_lo, int path_hi,
-                              uint4 rec_lo, uint4 rec_hi, int k, const uttt_state_t &s, float raw0, float raw1, float v,
-                              int &node_count, bool py = false, float *row = nullptr, bool has_sum = false,
-                              float known_sum = 0.0f, float *sum_out = nullptr, uint4 *root_out = nullptr) {
-    const int lane = lane_id();
-    const Legal g = legal_of(s);
-    const bool l0 = g.l0, l1 = g.l1;
-    const uint64_t b0 = g.b0, b1 = g.b1;
-    const int L = g.L, i0 = g.i0, i1 = g.i1;
-    const int nb = node_count;
-    const int blocks = py ? 1 : k;
-    if ((int64_t)nb + (int64_t)blocks * L > pool.cap || L == 0) return false;
-    const float p0 = l0 ? raw0 : 0.0f;
-    const float p1 = l1 ? raw1 : 0.0f;
-    float sum = 0.0f;
-    if (py) {
-        sum = np_sum_f32_legal(p0, p1, b0, b1, L);
-    } else if (has_sum) {
-        sum = known_sum;  // the cache record's (the same values added in the same order at insert)
-    } else if (row) {
-        sum = seq_sum_legal(row, p0, p1, g);
-    } else {
-        for (uint64_t bits = b0; bits; bits &= bits - 1ull) sum += readlane_f(p0, __builtin_ctzll(bits));
-        for (uint64_t bits = b1; bits; bits &= bits - 1ull) sum += readlane_f(p1, __builtin_ctzll(bits));
-    }
-    if (sum_out) *sum_out = sum;
-    const float un = 1.0f / (float)L;
-    const bool p64 = py && !(sum > 0);  // np.ones(float) / L: float64 priors
-    const float q0 = sum > 0 ? p0 / sum : un;
-    const float q1 = sum > 0 ? p1 / sum : un;
-    const uint4 c0 = new_child(q0, (uint32_t)lane), c1 = new_child(q1, (uint32_t)(64 + lane));
-    for (int j = 0; j < blocks; ++j) {
-        const size_t blk = base + nb + (size_t)j * L;
-        if (l0) pool.rec[blk + i0] = c0;
-        if (l1) pool.rec[blk + i1] = c1;
-    }
-    // the path, leaf (lane depth) to root: w += v k times with the sign flipping upwards, N += k; the
-    // leaf also gets its children's block size L and its link (first child, k copies: cpp k blocks,
-    // py one block); py: every node on the path now holds a float32 w (kMetaWF32), and the leaf's
-    // children carry float64 priors when the policy summed to zero (kMetaP64)
-    const uint32_t leaf_meta = (uint32_t)L << 23 | (py ? (kMetaWF32 | (p64 ? kMetaP64 : 0u)) : 0u);
-    const uint32_t leaf_link = make_link((uint32_t)nb, (uint32_t)k);
-    auto update = [&](uint4 r, int pn, int d) -> uint4 {  // path node pn at depth d, its record r
-        float w = __uint_as_float(r.x);
-        const float x = ((depth - d) & 1) ? -v : v;
-        for (int j = 0; j < k; ++j) w += x;
-        r.x = __float_as_uint(w);
-        r.z += (uint32_t)k;
-        if (py && d < depth) r.z |= kMetaWF32;
-        if (d == depth) {
-            r.z = (r.z & ~kMetaLMask) | leaf_meta;
-            r.w = leaf_link;
-        }
-        pool.rec[base + pn] = r;
-        return r;
-    };
-    uint4 new_lo = rec_lo;
-    if (lane <= depth) new_lo = update(rec_lo, path_lo, lane);
-    if (lane + 64 <= depth) update(rec_hi, path_hi, lane + 64);
-    if (root_out)  // the root's record as just written (lane 0 holds path[0])
-        *root_out = make_uint4((uint32_t)__builtin_amdgcn_readlane((int)new_lo.x, 0),
-                               (uint32_t)__builtin_amdgcn_readlane((int)new_lo.y, 0),
-                               (uint32_t)__builtin_amdgcn_readlane((int)new_lo.z, 0),
-                               (uint32_t)__builtin_amdgcn_readlane((int)new_lo.w, 0));
-    node_count = nb + blocks * L;
-    return true;
-}
-
-// ----------------------------------------------------------- root (begin) --
-// uttt_mcts.cpp:92-103: root expanded at once with uniform priors 1.0f/|legal|.
-// Self-play passes `live` (slot flags) and the slots' states in place (src_stride = sizeof(Slot)),
-// and err: the asynchronous move end's failure word, reset here (once per move, before this move's end,
-// after the previous move end's read of it) instead of by a memset on the stream, as is the search's
-// failure flag (Trees::count[3]);
-// search passes nullptr (all live) and packed states.
-
-// Tree t's root record, its uniform child block and its TreeCtl from the root state s (k_begin; k_search1 for
-// tree 0). py (pv_mcts.py:134): the root is a plain unexpanded node, evaluated by the first flush. on == false
-// (a self-play slot without a game): a root without children that is not live.
-__device__ __forceinline__ void init_root(const Pool &pool, const Trees &tr, int t, const uttt_state_t &s, bool on, int py) {
-    const int lane = lane_id();
-    const size_t base = (size_t)t * pool.cap;
-    const Legal g = legal_of(s, on || py);
-    const int L = py ? 0 : g.L;  // the child block's size
-    const float up = L ? 1.0f / (float)L : 0.0f;
-    if (!py && g.l0) pool.rec[base + 1 + g.i0] = new_child(up, (uint32_t)lane);
-    if (!py && g.l1) pool.rec[base + 1 + g.i1] = new_child(up, (uint32_t)(64 + lane));
-    if (lane == 0) {
-        pool.rec[base] = make_uint4(0u, 0u, make_meta(kNoAction, (uint32_t)L), make_link(L ? 1u : 0u, L ? 1u : 0u));
-        tr.root[t] = s;
-        TreeCtl c;
-        c.sims_done = 0;
-        c.node_count = 1 + L;
-        c.status = (on && g.L > 0) ? kLive : 0;
-        c.pad = 0;
-        tr.ctl[t] = c;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_begin(Pool pool, Trees tr, const char *src, int src_stride, const int32_t *live,
-                                                  unsigned long long *err) {
-    const int lane = lane_id();
-    const int t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    if (t == 0 && lane == 0) {
-        if (err) *err = ~0ull;
-        tr.count[2] = -1;  // a search starts: no round of it is known to be empty yet (k_round1's fast exit)
-        tr.count[3] = 0;   // and no tree of it has failed
-    }
-    if (t >= tr.n_trees) return;
-    const bool on = live ? (live[t] != 0) : true;
-    const uttt_state_t s = *reinterpret_cast<const uttt_state_t *>(src + (size_t)t * src_stride);
-    init_root(pool, tr, t, s, on, tr.py);
-}
 
 // --------------------------------------------------------------- select --
 // One wave per tree. uttt_mcts.cpp:109-127 for the simulations up to (and
