@@ -79,8 +79,10 @@ __device__ __forceinline__ void store_ranked_row(float *row /* LDS, 16-B aligned
     const int lane = lane_id();
     if (g.l0) row[g.i0] = p0;
     if (g.l1) row[g.i1] = p1;
-    // L4 - L < 4 <= 64: lanes L .. L4-1 pad (first item: no lane pads a row of 65-83 legal moves)
-    if (lane >= g.L && lane < ((g.L + 3) & ~3)) row[lane] = 0.0f;
+    // lanes 0 .. L4 - L - 1 (at most three) pad ranks L .. L4 - 1 (<= 83): by offset from L, so that a row of
+    // more than 64 legal moves is padded too (a lane index never reaches such a rank, and the row then kept
+    // what an earlier, wider leaf or another user of the LDS left there)
+    if (lane < ((g.L + 3) & ~3) - g.L) row[g.L + lane] = 0.0f;
 }
 __device__ __forceinline__ float sum_row4(const float *row, int L) {
     // the other lanes' stores before any lane's reads (LDS executes a wave's accesses in order; the
