@@ -136,6 +136,24 @@ int uttt_solve_host(const uttt_state_t *states, int64_t n, int32_t max_nodes, in
 int uttt_solve_overlay_host(const uttt_state_t *states, int64_t n, int32_t max_empties, int32_t max_nodes,
                             int32_t priors, float *policy, int64_t policy_ld, float *value, int64_t value_ld,
                             int8_t *status);
+/* The eight symmetries of the square (csrc/uttt_sym.h). g = r + 4 f, r in 0..3 quarter turns,
+ * f in 0..1 a mirror first: on the (9, 9) image np.rot90(np.fliplr(img) if f else img, k = r). beta_g is the
+ * same operation on a 3x3 index 3 R + C, and action a = 9 b + c goes to pi_g(a) = 9 beta_g(b) + beta_g(c).
+ * T_g moves bit a of own / opp to bit pi_g(a), bit b of each half of mains to bit beta_g(b), and the active
+ * board to beta_g(active) (-1 stays). An evaluator's policy row p' for T_g(s) is the row p[a] = p'[pi_g(a)]
+ * for s; the value is the same. */
+#define UTTT_SYM_COUNT 8
+/* out[a] = pi_g(a) */
+int uttt_sym_action_perm(int32_t g, int32_t out[81]);
+/* The symmetry k with T_k = T_g T_h (h first, pi_k = pi_g o pi_h), and the one with T_k T_g = identity;
+ * UTTT_ERR_ARG (negative) for a symmetry outside 0..7. */
+int uttt_sym_compose(int32_t g, int32_t h);
+int uttt_sym_inverse(int32_t g);
+/* out[i] = T_{sym[i]}(states[i]); out may be states. */
+int uttt_states_transform_host(const uttt_state_t *states, int64_t n, const int8_t *sym, uttt_state_t *out);
+/* The hashed choice: sym[i] = the top three bits of the playout key (csrc/uttt_playout.h) of state i's 243
+ * network-input bits and `seed`: a function of the stones, the legal moves and the seed alone. */
+int uttt_states_symmetry_host(const uttt_state_t *states, int64_t n, uint64_t seed, int8_t *sym);
 
 /* --------------------------------------------------------------- engine --- */
 typedef struct uttt_engine uttt_engine_t;
@@ -283,6 +301,29 @@ int uttt_solve(uttt_engine_t *eng, const uttt_state_t *states, int64_t n, int32_
  * they do). One row per leaf: per-copy applies are out of scope. */
 int uttt_eval_solve_dev(uttt_engine_t *eng, int32_t max_empties, int32_t max_nodes, int32_t priors, float *policy,
                         int64_t policy_ld, float *value, int64_t value_ld, int8_t *status);
+/* The round's pending leaves seen through a symmetry (the count read on the device, as uttt_eval_playout_dev;
+ * after uttt_search_select or uttt_search_select_async): states_out[r] = T_g(leaf r), sym_out[r] = g, and,
+ * unless nn_input_out is NULL, row r of nn_input_out = the NCHW (3, 9, 9) network input of T_g(leaf r).
+ * mode UTTT_SYM_FIXED: g = g_or_seed (0..7) for every leaf; UTTT_SYM_HASHED: g = uttt_states_symmetry_host's
+ * choice for the leaf with seed g_or_seed. states_out: max_trees states, sym_out: max_trees int8,
+ * nn_input_out: max_trees * 243 f32, device memory; rows past the count are untouched. One wave per leaf on
+ * the engine's stream. */
+#define UTTT_SYM_FIXED 0
+#define UTTT_SYM_HASHED 1
+int uttt_sym_pending_dev(uttt_engine_t *eng, int32_t mode, uint64_t g_or_seed, uttt_state_t *states_out,
+                         int8_t *sym_out, float *nn_input_out);
+/* An evaluator's rows for transformed leaves mapped back (the count read on the device, as above): for row r
+ * below the count and g = sym[r],
+ *   out_policy[r * out_policy_ld + a] = (policy[r * policy_ld + pi_g(a)] [+ out_policy[...] if accumulate]) [* scale]
+ *   out_value[r * out_value_ld]       = (value[r * value_ld]             [+ out_value[...]  if accumulate]) [* scale]
+ * in f32, the multiplication only when scale != 1. Without accumulate the row is a plain permuted copy. No
+ * output buffer may overlap an input buffer (checked over one row per tree of the search: UTTT_ERR_ARG); the
+ * leading dimensions of the policies are >= 81, the value
+ * strides >= 1 (as uttt_eval_solve_dev). Rows past the count are untouched. One wave per row on the engine's
+ * stream. */
+int uttt_sym_rows_dev(uttt_engine_t *eng, const int8_t *sym, const float *policy, int64_t policy_ld,
+                      const float *value, int64_t value_ld, float *out_policy, int64_t out_policy_ld,
+                      float *out_value, int64_t out_value_ld, int32_t accumulate, float scale);
 /* One whole round with the hash evaluator, enqueued by one call (round 5; the rounds of
  * SelfPlay.steps with HashEvaluator lanes, i.e. the kernel microbenchmark of SURVEY §8(d)):
  * uttt_search_select_async_tag(ring_slot, tag) -> uttt_eval_hash_dev(policy, value) ->
@@ -386,7 +427,7 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
 /* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve,
- * 17 solve_leaves.
+ * 17 solve_leaves, 18 sym_leaves, 19 sym_rows.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

@@ -42,6 +42,11 @@ int uttt_nn_stem(uttt_engine_t *eng, const float *w, const float *b, float *out)
  * pv_mcts_scores flush), on `stream`. */
 int uttt_nn_stem_states(const uttt_state_t *states, int32_t n, const float *w, const float *b, float *out,
                         void *stream);
+/* The same from a device buffer of max_n packed states of which the first min(*n_dev, max_n) count, the
+ * count read on the device (e.g. uttt_sym_pending_dev's states_out and uttt_search_count_ptr): the grid is
+ * sized for max_n and rows past the count are not touched. */
+int uttt_nn_stem_states_dev(const uttt_state_t *states, const int32_t *n_dev, int32_t max_n, const float *w,
+                            const float *b, float *out, void *stream);
 /* Policy softmax (n,81) (logits if softmax == 0) and tanh value (n) from the final
  * activation (n,81,128) (dual_network.py:106-121). */
 int uttt_nn_heads(const float *act, const float *head_weights, int32_t n, float *policy, float *value,

@@ -26,6 +26,7 @@
 //   wave.h    lane / wave helpers, DPP arg-max, host-visible stores
 //   cache.h   EvalCache: probe, lookup, insert
 //   expand.h  legal masks, f32 sums, expand_backup, init_root, k_begin
+//   symmetry.h  k_sym_leaves, k_sym_rows: the pending leaves through a symmetry, the rows mapped back
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -42,11 +43,13 @@
 #include "uttt_engine.h"
 #include "uttt_playout.h"
 #include "uttt_solve.h"
+#include "uttt_sym.h"
 
 #include "engine/layout.h"
 #include "engine/wave.h"
 #include "engine/cache.h"
 #include "engine/expand.h"
+#include "engine/symmetry.h"
 
 namespace uttt {
 
@@ -3108,6 +3111,62 @@ int uttt_eval_solve_dev(uttt_engine_t *e, int32_t max_empties, int32_t max_nodes
     HIP_TRY(hipSetDevice(e->device));
     timed_launch(e, kKSolveLeaves, k_solve_leaves, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, max_empties,
                  max_nodes, priors, policy, policy_ld, value, value_ld, status);
+    return check_launch();
+}
+
+int uttt_sym_pending_dev(uttt_engine_t *e, int32_t mode, uint64_t g_or_seed, uttt_state_t *states_out, int8_t *sym_out,
+                         float *nn_input_out) {
+    if (!e || !states_out || !sym_out) {
+        set_error("uttt_sym_pending_dev: null engine, states_out or sym_out");
+        return UTTT_ERR_ARG;
+    }
+    if (mode != UTTT_SYM_FIXED && mode != UTTT_SYM_HASHED) {
+        set_error("mode must be UTTT_SYM_FIXED (0) or UTTT_SYM_HASHED (1) (got %d)", mode);
+        return UTTT_ERR_ARG;
+    }
+    if (mode == UTTT_SYM_FIXED && g_or_seed >= (uint64_t)kSymCount) {
+        set_error("a fixed symmetry must be 0..%d (got %llu)", kSymCount - 1, (unsigned long long)g_or_seed);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    timed_launch(e, kKSymLeaves, k_sym_leaves, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, mode, g_or_seed,
+                 states_out, sym_out, nn_input_out);
+    return check_launch();
+}
+
+// [a, a + rows * ld) and [b, b + rows * ld_b) share a float
+static bool rows_overlap(const float *a, int64_t ld_a, const float *b, int64_t ld_b, int64_t rows) {
+    return a < b + rows * ld_b && b < a + rows * ld_a;
+}
+
+int uttt_sym_rows_dev(uttt_engine_t *e, const int8_t *sym, const float *policy, int64_t policy_ld, const float *value,
+                      int64_t value_ld, float *out_policy, int64_t out_policy_ld, float *out_value,
+                      int64_t out_value_ld, int32_t accumulate, float scale) {
+    if (!e || !sym || !policy || !value || !out_policy || !out_value) {
+        set_error("uttt_sym_rows_dev: null pointer");
+        return UTTT_ERR_ARG;
+    }
+    if (policy_ld < 81 || out_policy_ld < 81) {
+        set_error("policy_ld must be at least 81 (got %lld and %lld)", (long long)policy_ld, (long long)out_policy_ld);
+        return UTTT_ERR_ARG;
+    }
+    if (value_ld < 1 || out_value_ld < 1) {
+        set_error("value_ld must be at least 1 (got %lld and %lld)", (long long)value_ld, (long long)out_value_ld);
+        return UTTT_ERR_ARG;
+    }
+    // the kernel reads and writes at most one row per tree of the search: over that many rows no output may
+    // share a float with an input (a value column may lie inside its own policy's padding, not the other's)
+    const int64_t rows = e->tr.n_trees > 0 ? e->tr.n_trees : 1;
+    if (rows_overlap(policy, policy_ld, out_policy, out_policy_ld, rows) ||
+        rows_overlap(value, value_ld, out_value, out_value_ld, rows) ||
+        rows_overlap(policy, policy_ld, out_value, out_value_ld, rows) ||
+        rows_overlap(value, value_ld, out_policy, out_policy_ld, rows)) {
+        set_error("uttt_sym_rows_dev: the output buffers overlap the input buffers (over %lld rows)", (long long)rows);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    timed_launch(e, kKSymRows, k_sym_rows, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->tr, sym, policy, policy_ld,
+                 value, value_ld, out_policy, out_policy_ld, out_value, out_value_ld, accumulate ? 1 : 0, scale);
     return check_launch();
 }
 

@@ -67,9 +67,11 @@ enum KernelId {
     kKPlayout,  // k_playout_leaves / k_playout_states launches
     kKSolve,    // k_solve_states launches
     kKSolveLeaves,  // k_solve_leaves launches
+    kKSymLeaves,    // k_sym_leaves launches
+    kKSymRows,      // k_sym_rows launches
     kKernelCount
 };
-static_assert(kKSolveLeaves == 17, "the public header and _lib.KERNELS state the ids");
+static_assert(kKSolveLeaves == 17 && kKSymRows == 19, "the public header and _lib.KERNELS state the ids");
 
 // Device counters are striped: counter i of a row lives in kStripes 128-byte slots, and a workgroup
 // adds into slot (blockIdx & (kStripes - 1)), so thousands of waves finishing together do not

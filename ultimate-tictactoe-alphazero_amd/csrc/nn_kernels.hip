@@ -254,6 +254,23 @@ int uttt_nn_stem_states(const uttt_state_t *states, int32_t n, const float *w, c
     return UTTT_OK;
 }
 
+int uttt_nn_stem_states_dev(const uttt_state_t *states, const int32_t *n_dev, int32_t max_n, const float *w,
+                            const float *b, float *out, void *stream) {
+    if (!states || !n_dev || !w || !b || !out || max_n < 0) {
+        set_error("uttt_nn_stem_states_dev: bad arguments");
+        return UTTT_ERR_ARG;
+    }
+    if (max_n == 0) return UTTT_OK;
+    hipLaunchKernelGGL(nn::k_stem, dim3((max_n + nn::SB - 1) / nn::SB), dim3(256), 0, (hipStream_t)stream, states, nullptr,
+                       max_n, n_dev, w, b, out);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) {
+        set_error("k_stem launch: %s", hipGetErrorString(r));
+        return UTTT_ERR_HIP;
+    }
+    return UTTT_OK;
+}
+
 int uttt_nn_heads(const float *act, const float *head_weights, int32_t n, float *policy, float *value, int32_t softmax,
                   void *stream) {
     if (!act || !head_weights || !policy || !value || n < 0) {

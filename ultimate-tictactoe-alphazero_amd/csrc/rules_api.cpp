@@ -11,6 +11,7 @@
 #include "uttt_engine.h"
 #include "uttt_playout.h"
 #include "uttt_solve.h"
+#include "uttt_sym.h"
 
 namespace uttt {
 // Last error of the calling thread, for every entry point of the C ABI (uttt_last_error).
@@ -344,6 +345,69 @@ int uttt_solve_overlay_host(const uttt_state_t *states, int64_t n, int32_t max_e
             }
         }
         if (status) status[i] = st;
+    }
+    return UTTT_OK;
+}
+
+static int check_sym(const char *who, int32_t g) {
+    if (g < 0 || g >= kSymCount) {
+        set_error("%s: a symmetry must be 0..%d (got %d)", who, kSymCount - 1, g);
+        return UTTT_ERR_ARG;
+    }
+    return UTTT_OK;
+}
+
+int uttt_sym_action_perm(int32_t g, int32_t out[81]) {
+    if (int rc = check_sym("uttt_sym_action_perm", g)) return rc;
+    if (!out) {
+        set_error("uttt_sym_action_perm: null pointer");
+        return UTTT_ERR_ARG;
+    }
+    for (int a = 0; a < 81; ++a) out[a] = sym_action(g, a);
+    return UTTT_OK;
+}
+
+int uttt_sym_compose(int32_t g, int32_t h) {
+    if (int rc = check_sym("uttt_sym_compose", g)) return rc;
+    if (int rc = check_sym("uttt_sym_compose", h)) return rc;
+    return sym_compose(g, h);
+}
+
+int uttt_sym_inverse(int32_t g) {
+    if (int rc = check_sym("uttt_sym_inverse", g)) return rc;
+    return sym_inverse(g);
+}
+
+static int check_sym_states(const char *who, const uttt_state_t *states, int64_t n, const void *a, const void *b) {
+    if (n < 0 || ((!states || !a || !b) && n > 0)) {
+        set_error("%s: null pointer or negative count", who);
+        return UTTT_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (states[i].active < -1 || states[i].active > 8) {
+            set_error("active_board must be -1..8 (state %lld has %d)", (long long)i, states[i].active);
+            return UTTT_ERR_ARG;
+        }
+    }
+    return UTTT_OK;
+}
+
+int uttt_states_transform_host(const uttt_state_t *states, int64_t n, const int8_t *sym, uttt_state_t *out) {
+    // T_g of uttt_sym.h for n states; what k_sym_leaves writes.
+    if (int rc = check_sym_states("uttt_states_transform_host", states, n, sym, out)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (int rc = check_sym("uttt_states_transform_host", sym[i])) return rc;
+    for (int64_t i = 0; i < n; ++i) out[i] = sym_state(states[i], sym[i]);
+    return UTTT_OK;
+}
+
+int uttt_states_symmetry_host(const uttt_state_t *states, int64_t n, uint64_t seed, int8_t *sym) {
+    // The hashed choice of uttt_sym.h; what k_sym_leaves chooses in UTTT_SYM_HASHED.
+    if (int rc = check_sym_states("uttt_states_symmetry_host", states, n, sym, sym)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        uint64_t w[4];
+        input_words(states[i], w);
+        sym[i] = (int8_t)sym_of_key(w, seed);
     }
     return UTTT_OK;
 }

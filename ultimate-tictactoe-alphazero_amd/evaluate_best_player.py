@@ -18,6 +18,7 @@ import uttt_cpp  # noqa: E402
 import pv_mcts  # noqa: E402
 from pv_mcts import pv_mcts_action  # noqa: E402
 from uttt_amd import arena  # noqa: E402
+from uttt_amd.selfplay import symmetry_from_env  # noqa: E402
 from uttt_amd.model import DualNetwork  # noqa: E402
 
 CPP_GAME_AVAILABLE = True
@@ -106,8 +107,10 @@ def evaluate_best_player():
     next_pv_mcts_action = pv_mcts_action(model, 0.0)
     point = evaluate_algorithm_of("VS_Random", (next_pv_mcts_action, random_action))
     if EP_VS_MCTS:
+        # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed: the model's leaves only
         print("VS_MCTS", arena.evaluate_vs_playouts(model, EP_GAME_COUNT, evaluate_count=pv_mcts.PV_EVALUATE_COUNT,
-                                                    batch_size=pv_mcts.MCTS_BATCH_SIZE)[0])
+                                                    batch_size=pv_mcts.MCTS_BATCH_SIZE,
+                                                    symmetry=symmetry_from_env())[0])
     if EP_VS_ALPHABETA:
         evaluate_algorithm_of("VS_AlphaBeta", (next_pv_mcts_action, alpha_beta_action_factory()))
     del model

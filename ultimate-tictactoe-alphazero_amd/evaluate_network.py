@@ -19,6 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import uttt_cpp  # noqa: E402
 from uttt_amd import arena  # noqa: E402
+from uttt_amd.selfplay import symmetry_from_env  # noqa: E402
 from uttt_amd.model import DualNetwork  # noqa: E402
 
 CPP_GAME_AVAILABLE = True
@@ -57,8 +58,9 @@ def evaluate_network():
     def progress(done, total):
         print("\rEvaluate {}/{}".format(done, total), end="")
 
+    # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed: leaves seen through a symmetry
     average_point, _, _ = arena.evaluate_network(model0, model1, EN_GAME_COUNT, EN_TEMPERATURE, seed_base,
-                                                 progress=progress)
+                                                 progress=progress, symmetry=symmetry_from_env())
     print("")
     print("AveragePoint", average_point)
     del model0

@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import uttt_cpp  # noqa: E402
 from pv_mcts import pv_mcts_scores  # noqa: E402
 from uttt_amd import arena  # noqa: E402
+from uttt_amd.selfplay import symmetry_from_env  # noqa: E402
 from uttt_amd.model import DN_INPUT_SHAPE, DualNetwork  # noqa: E402,F401
 
 DN_OUTPUT_SIZE = 81
@@ -71,7 +72,9 @@ def self_play():
     def progress(done, total):
         print("\rSelfPlay {}/{}".format(done, total), end="")
 
-    games = arena.self_play_py(model, SP_GAME_COUNT, seed_base, SP_TEMPERATURE, progress=progress)
+    # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed: leaves seen through a symmetry
+    games = arena.self_play_py(model, SP_GAME_COUNT, seed_base, SP_TEMPERATURE, progress=progress,
+                               symmetry=symmetry_from_env())
     print("")
     history = [rec for g in games for rec in g]
     write_data(history)

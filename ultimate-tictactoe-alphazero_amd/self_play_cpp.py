@@ -40,7 +40,7 @@ except ImportError:
 from uttt_amd.model import DualNetwork  # noqa: E402
 from uttt_amd.distributed import broadcast_int, init_from_env, self_play_sharded  # noqa: E402
 from uttt_amd.history import write_history_file  # noqa: E402
-from uttt_amd.selfplay import SelfPlay, default_lanes, history_from_records  # noqa: E402
+from uttt_amd.selfplay import SelfPlay, default_lanes, history_from_records, symmetry_from_env  # noqa: E402
 
 SP_GAME_COUNT = 500
 SP_TEMPERATURE = 1.0
@@ -59,11 +59,12 @@ def _fingerprint(model):
 
 def _runner(model, slots):
     """One cached single-game runner per model (rebuilt when its weights change)."""
-    key = (id(model), slots, _fingerprint(model))
+    sym = symmetry_from_env()  # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed
+    key = (id(model), slots, _fingerprint(model), sym)
     r = _single.get("runner") if _single.get("key") == key else None
     if r is None:
         _single.clear()
-        r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, model=model)
+        r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, model=model, symmetry=sym)
         _single.update(key=key, runner=r)
     return r
 
@@ -134,11 +135,12 @@ def self_play(use_cpp=True, n_games=None, slots=None, seed_base=None, model_path
     t0 = time.perf_counter()
     if world > 1:
         recs = self_play_sharded(model, n_games, slots, seed_base, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE,
-                                 SP_TEMPERATURE, lanes=lanes, progress=progress, timings=LAST_TIMINGS)
+                                 SP_TEMPERATURE, lanes=lanes, progress=progress, timings=LAST_TIMINGS,
+                                 symmetry=symmetry_from_env())
     else:
         n_lanes = default_lanes(slots) if lanes is None else lanes
         r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, device=dev.index, model=model,
-                     lanes=n_lanes)
+                     lanes=n_lanes, symmetry=symmetry_from_env())
         LAST_TIMINGS["setup_s"] = time.perf_counter() - t0
         LAST_TIMINGS["games_s"] = r.run(0, n_games, seed_base, progress)
         LAST_TIMINGS["sims"] = r.sims

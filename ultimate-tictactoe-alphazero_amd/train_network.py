@@ -64,7 +64,9 @@ def train_network():
     t1 = time.perf_counter()
     model = DualNetwork().to(dev)
     model.load_state_dict(torch.load("./model/best.pth", map_location=dev, weights_only=True))
-    losses = _train.train_network(model, history, RN_EPOCHS, BATCH_SIZE, dev)
+    # UTTT_TRAIN_AUGMENT=1: each epoch trains on a fresh random symmetry image of every sample
+    losses = _train.train_network(model, history, RN_EPOCHS, BATCH_SIZE, dev,
+                                  augment=os.environ.get("UTTT_TRAIN_AUGMENT", "0") == "1")
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t2 = time.perf_counter()

@@ -17,7 +17,7 @@ if PKG_ROOT not in sys.path:  # makes `import uttt_cpp` resolve to the in-tree m
 
 from .engine import Engine, as_states, initial_states  # noqa: E402
 from .selfplay import (BatchedSearch, HashEvaluator, NetworkEvaluator, PlayoutEvaluator, SelfPlay,  # noqa: E402
-                       SolvedLeaves, history_from_records)
+                       SolvedLeaves, SymmetricLeaves, history_from_records)
 
 __all__ = ["Engine", "as_states", "initial_states", "BatchedSearch", "SelfPlay", "HashEvaluator",
-           "PlayoutEvaluator", "SolvedLeaves", "NetworkEvaluator", "history_from_records", "PKG_ROOT"]
+           "PlayoutEvaluator", "SolvedLeaves", "SymmetricLeaves", "NetworkEvaluator", "history_from_records", "PKG_ROOT"]

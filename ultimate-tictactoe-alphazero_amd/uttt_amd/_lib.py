@@ -18,7 +18,7 @@ ERRORS = {-1: "UTTT_ERR_ARG", -2: "UTTT_ERR_HIP", -3: "UTTT_ERR_CAPACITY", -4: "
           -5: "UTTT_ERR_NODEVICE", -6: "UTTT_ERR_NONFINITE"}
 
 KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15, "solve": 16,
-           "solve_leaves": 17,
+           "solve_leaves": 17, "sym_leaves": 18, "sym_rows": 19,
            # select latency counters (their value is in "bytes"; no launches)
            "select_levels": 6, "select_trees": 7, "select_max_levels_sum": 9,
            "select_trips": 10, "select_max_trips_sum": 12}
@@ -67,6 +67,13 @@ SIGNATURES = {
     "uttt_playout_host": (ctypes.c_int, [_SP, _I64, _I32, _U64, _I32P, _I32P]),
     "uttt_solve_host": (ctypes.c_int, [_SP, _I64, _I32, _I8P, _I8P, _I8P, _I64P, _I8P]),
     "uttt_solve_overlay_host": (ctypes.c_int, [_SP, _I64, _I32, _I32, _I32, _F32P, _I64, _F32P, _I64, _I8P]),
+    "uttt_sym_action_perm": (ctypes.c_int, [_I32, _I32P]),
+    "uttt_sym_compose": (ctypes.c_int, [_I32, _I32]),
+    "uttt_sym_inverse": (ctypes.c_int, [_I32]),
+    "uttt_states_transform_host": (ctypes.c_int, [_SP, _I64, _I8P, _SP]),
+    "uttt_states_symmetry_host": (ctypes.c_int, [_SP, _I64, _U64, _I8P]),
+    "uttt_sym_pending_dev": (ctypes.c_int, [_P, _I32, _U64, _P, _P, _P]),
+    "uttt_sym_rows_dev": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _F32]),
     "uttt_engine_create": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_P)]),
     "uttt_engine_destroy": (ctypes.c_int, [_P]),
     "uttt_engine_share_cache": (ctypes.c_int, [_P, _P]),
@@ -116,6 +123,7 @@ SIGNATURES = {
     "uttt_engine_cache_stats2": (ctypes.c_int, [_P, _I64P, _I64P, _I64P, _I64P]),
     "uttt_nn_stem": (ctypes.c_int, [_P, _P, _P, _P]),
     "uttt_nn_stem_states": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P]),
+    "uttt_nn_stem_states_dev": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _P]),
     "uttt_nn_heads": (ctypes.c_int, [_P, _P, _I32, _P, _P, _I32, _P]),
     "uttt_nn_heads_dev": (ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _P]),
     "uttt_nn_wino3h_weights": (ctypes.c_int, [_F32P, _P, ctypes.POINTER(ctypes.c_float)]),

@@ -81,19 +81,23 @@ class ModelEvaluator:
         return p.to(x.device).float(), v.to(x.device).float().reshape(n, -1)
 
 
-def model_evaluator(model, max_batch=None, engine=None, kind=None):
+def model_evaluator(model, max_batch=None, engine=None, kind=None, symmetry=None):
     """Engine evaluator for a model: the fused HIP evaluator for a DualNetwork (given the engine;
     nnfast.evaluator_kind), else NetworkEvaluator when the model lives on the GPU (no copies),
-    ModelEvaluator otherwise."""
+    ModelEvaluator otherwise. symmetry (selfplay.parse_symmetry's forms; default off; needs the engine): the
+    evaluator wrapped in SymmetricLeaves."""
+    from .selfplay import parse_symmetry, with_symmetry
+    if parse_symmetry(symmetry) is not None and engine is None:
+        raise ValueError("model_evaluator: symmetry needs the engine whose leaves are transformed")
     if engine is not None:
         from .nnfast import FusedNetworkEvaluator, evaluator_kind
         if evaluator_kind(model, kind) == "fused":
-            return FusedNetworkEvaluator(model, engine)
+            return with_symmetry(FusedNetworkEvaluator(model, engine), engine, symmetry)
     dev = next((p.device for p in model.parameters()), None)
     if dev is not None and dev.type == "cuda" and max_batch:
         model.eval()
-        return NetworkEvaluator(model, max_batch)
-    return ModelEvaluator(model)
+        return with_symmetry(NetworkEvaluator(model, max_batch), engine, symmetry)
+    return with_symmetry(ModelEvaluator(model), engine, symmetry)
 
 
 def _play_games(searches, evaluators, evaluate_counts, game_count, temperature, seed_base, batch_size, progress):
@@ -131,15 +135,16 @@ def _play_games(searches, evaluators, evaluate_counts, game_count, temperature, 
 
 
 def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0, evaluate_count=50,
-                     batch_size=8, device=None, make_evaluator=None, progress=None):
+                     batch_size=8, device=None, make_evaluator=None, progress=None, symmetry=None):
     """evaluate_network.py:58-104 with all games concurrent. Game g: model0 moves first when g is
     even, model1 when odd (:78-82). Returns (model0's average point, per-game first-player points,
     per-game action lists). make_evaluator(model, engine) -> engine evaluator (default: the model
-    called on the engine's input batch; e.g. nnfast.FusedNetworkEvaluator for a DualNetwork)."""
+    called on the engine's input batch; e.g. nnfast.FusedNetworkEvaluator for a DualNetwork). symmetry: the
+    default evaluators' SymmetricLeaves setting (model_evaluator; default off)."""
     searches = [PvMcts(game_count, evaluate_count, device) for _ in range(2)]
     if make_evaluator is None:
-        evaluators = (model_evaluator(model0, game_count, searches[0].engine),
-                      model_evaluator(model1, game_count, searches[1].engine))
+        evaluators = (model_evaluator(model0, game_count, searches[0].engine, symmetry=symmetry),
+                      model_evaluator(model1, game_count, searches[1].engine, symmetry=symmetry))
     else:
         evaluators = (make_evaluator(model0, searches[0].engine), make_evaluator(model1, searches[1].engine))
     return _play_games(searches, evaluators, (evaluate_count, evaluate_count), game_count, temperature, seed_base,
@@ -148,7 +153,7 @@ def evaluate_network(model0, model1, game_count=50, temperature=1.0, seed_base=0
 
 def evaluate_vs_playouts(model, game_count=10, playouts=64, opponent_evaluate_count=1000, seed_base=0,
                          temperature=0.0, evaluate_count=50, batch_size=8, device=None, make_evaluator=None,
-                         playout_seed=0, progress=None, opponent_solve=None):
+                         playout_seed=0, progress=None, opponent_solve=None, symmetry=None):
     """The model's PV-MCTS player against plain MCTS over random playouts (the reference's commented-out
     VS_MCTS opponent, evaluate_best_player.py:93-95 with game.py:294-379's mcts_action: there UCB1 over one
     playout per evaluation, here the same search as the model's with PlayoutEvaluator in place of the network:
@@ -161,7 +166,7 @@ def evaluate_vs_playouts(model, game_count=10, playouts=64, opponent_evaluate_co
     (SolvedLeaves.counts: {"skipped", "solved", "budget"})."""
     searches = [PvMcts(game_count, evaluate_count, device), PvMcts(game_count, opponent_evaluate_count, device)]
     if make_evaluator is None:
-        ev = model_evaluator(model, game_count, searches[0].engine)
+        ev = model_evaluator(model, game_count, searches[0].engine, symmetry=symmetry)
     else:
         ev = make_evaluator(model, searches[0].engine)
     opponent = PlayoutEvaluator(searches[1].engine, playouts, playout_seed)
@@ -182,14 +187,15 @@ def first_player_value(state):
 
 
 def self_play_py(model, game_count, seed_base=0, temperature=1.0, evaluate_count=50, batch_size=8, device=None,
-                 make_evaluator=None, progress=None):
+                 make_evaluator=None, progress=None, symmetry=None):
     """self_play.py:66-99 (the Python self-play: pv_mcts.py searches) for game_count games at once.
     Game g draws from RandomState(seed_base + g) (= play(model) after np.random.seed(seed_base + g)).
     Returns one history per game: [input (9,9,3) float64, policies (81 Python floats, 0 for
     illegal actions), value (first_player_value at ply 0, then alternating)]."""
     import uttt_cpp
     search = PvMcts(game_count, evaluate_count, device)
-    ev = make_evaluator(model, search.engine) if make_evaluator else model_evaluator(model, game_count, search.engine)
+    ev = make_evaluator(model, search.engine) if make_evaluator else \
+        model_evaluator(model, game_count, search.engine, symmetry=symmetry)
     states = [uttt_cpp.State() for _ in range(game_count)]
     rngs = [np.random.RandomState(seed_base + g) for g in range(game_count)]
     hist = [[] for _ in range(game_count)]

@@ -230,6 +230,75 @@ class Engine:
                                            ctypes.c_void_p(value.data_ptr()), value.stride(0),
                                            ctypes.c_void_p(status.data_ptr()) if status is not None else None))
 
+    SYM_MODES = {"fixed": 0, "hashed": 1}
+
+    def sym_pending_dev(self, mode, g_or_seed, states_out, sym_out, nn_input_out=None):
+        """The round's pending leaves through a symmetry (uttt_sym_pending_dev: states and count on the device,
+        after select or select_async): states_out[r] = T_g(leaf r), sym_out[r] = g and, when given,
+        nn_input_out[r] = the image's NCHW input. mode "fixed": g = g_or_seed (0..7); "hashed": the
+        position-keyed choice with seed g_or_seed. states_out: (max_trees, 8) int32, sym_out: (max_trees,) int8,
+        nn_input_out: (max_trees, 3, 9, 9) f32, contiguous device tensors."""
+        import torch
+
+        if mode not in self.SYM_MODES:
+            raise ValueError(f"sym_pending_dev: mode must be 'fixed' or 'hashed' (got {mode!r})")
+        if mode == "fixed" and not 0 <= int(g_or_seed) <= 7:
+            raise ValueError(f"sym_pending_dev: a fixed symmetry must be 0..7 (got {g_or_seed})")
+        for name, t, dtype, numel in (("states_out", states_out, torch.int32, 8), ("sym_out", sym_out, torch.int8, 1),
+                                      ("nn_input_out", nn_input_out, torch.float32, 243)):
+            if t is None and name == "nn_input_out":
+                continue
+            if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise ValueError(f"sym_pending_dev: {name} must be a contiguous {dtype} device tensor")
+            if t.numel() < self.max_trees * numel:
+                raise ValueError(f"sym_pending_dev: {name} must hold {numel} entries for each of the engine's "
+                                 f"{self.max_trees} trees")
+        check(self.lib.uttt_sym_pending_dev(self.h, self.SYM_MODES[mode],
+                                            ctypes.c_uint64(int(g_or_seed) & 0xFFFFFFFFFFFFFFFF),
+                                            ctypes.c_void_p(states_out.data_ptr()), ctypes.c_void_p(sym_out.data_ptr()),
+                                            ctypes.c_void_p(nn_input_out.data_ptr()) if nn_input_out is not None
+                                            else None))
+
+    def sym_rows_dev(self, sym, policy, value, out_policy, out_value, accumulate=False, scale=1.0):
+        """An evaluator's rows for transformed leaves mapped back (uttt_sym_rows_dev: the count on the device):
+        out_policy[r, a] = (out_policy[r, a] if accumulate else nothing) + policy[r, pi_sym[r](a)], the same for
+        the value, both times `scale` when it is not 1. policy / out_policy: (rows, >=81) f32 and value /
+        out_value: (rows,) or (rows, 1) f32 device tensors, passed with their row strides, the outputs distinct
+        from the inputs; sym: (rows,) int8, contiguous."""
+        import torch
+
+        for name, pol, val in (("", policy, value), ("out_", out_policy, out_value)):
+            if not (pol.is_cuda and val.is_cuda and pol.dtype == torch.float32 and val.dtype == torch.float32):
+                raise ValueError(f"sym_rows_dev: {name}policy and {name}value must be float32 device tensors")
+            if pol.dim() != 2 or pol.shape[1] < 81 or pol.stride(1) != 1:
+                raise ValueError(f"sym_rows_dev: {name}policy must be (rows, >=81) with unit stride along the actions")
+            if val.dim() not in (1, 2) or (val.dim() == 2 and val.shape[1] != 1) or len(val) != len(pol):
+                raise ValueError(f"sym_rows_dev: {name}value must be (rows,) or (rows, 1), one per policy row")
+        if len(out_policy) != len(policy):
+            raise ValueError("sym_rows_dev: policy and out_policy must have the same rows")
+        # the kernel writes every row below the device's count: the host's copy of it when it has one, else
+        # at most every tree of the search
+        need = self.n_pending if self.n_pending is not None else self.n_trees
+        if len(policy) < need:
+            raise ValueError(f"sym_rows_dev: {len(policy)} rows for up to {need} pending leaves")
+
+        def span(t):  # the bytes the tensor's rows cover, padding between rows included
+            return t.data_ptr(), t.data_ptr() + 4 * ((len(t) - 1) * t.stride(0) + (t.shape[1] if t.dim() == 2 else 1))
+
+        for src in (policy, value):
+            for dst in (out_policy, out_value):
+                (a0, a1), (b0, b1) = span(src), span(dst)
+                if a0 < b1 and b0 < a1:
+                    raise ValueError("sym_rows_dev: the outputs must not overlap the inputs")
+        if not (sym.is_cuda and sym.dtype == torch.int8 and sym.is_contiguous()) or sym.numel() < len(policy):
+            raise ValueError("sym_rows_dev: sym must be a contiguous int8 device tensor, one entry per row")
+        check(self.lib.uttt_sym_rows_dev(self.h, ctypes.c_void_p(sym.data_ptr()),
+                                         ctypes.c_void_p(policy.data_ptr()), policy.stride(0),
+                                         ctypes.c_void_p(value.data_ptr()), value.stride(0),
+                                         ctypes.c_void_p(out_policy.data_ptr()), out_policy.stride(0),
+                                         ctypes.c_void_p(out_value.data_ptr()), out_value.stride(0),
+                                         int(bool(accumulate)), float(scale)))
+
     def rounds_hash_async(self, ring_slot, policy, value, n_rounds):
         """n_rounds consecutive hash rounds in one call (uttt_rounds_hash_async): ring slots ring_slot ..
         ring_slot + n_rounds - 1 (mod 8), tags tag + 1 .. tag + n_rounds; returns the last round's tag."""

@@ -210,6 +210,32 @@ class FusedNetworkEvaluator:
                                            self._stream()))
         return self._tower_heads(n, softmax)
 
+    @torch.no_grad()
+    def forward_device_states(self, states_dev, n, softmax=True):
+        """Evaluate packed states already on the device: states_dev a contiguous (>= max_batch, 8) int32 tensor
+        (e.g. Engine.sym_pending_dev's states_out), n an int or, with an engine, a RoundCount (the count read
+        on the device, uttt_nn_stem_states_dev). The stem reads the buffer; the tower and the heads are
+        forward()'s, and so is the return value."""
+        if not (states_dev.is_cuda and states_dev.dtype == torch.int32 and states_dev.is_contiguous()):
+            raise ValueError("forward_device_states: states_dev must be a contiguous int32 device tensor")
+        if states_dev.numel() < 8 * self.max_batch:
+            raise ValueError(f"forward_device_states: states_dev must hold max_batch = {self.max_batch} states")
+        if isinstance(n, RoundCount):
+            if self.engine is None:
+                raise ValueError("forward_device_states: a RoundCount needs the evaluator's engine")
+            n_dev = self.engine.count_ptr()
+            check(self.lib.uttt_nn_stem_states_dev(_p(states_dev), n_dev, self.max_batch, _p(self.stem_w),
+                                                   _p(self.stem_b), _p(self.buf[0]), self._stream()))
+            return self._tower_heads(n, softmax, n_dev=n_dev)
+        n = int(n)
+        if not 0 <= n <= self.max_batch:
+            raise ValueError(f"{n} states outside 0..max_batch {self.max_batch}")
+        if n == 0:
+            return self.policy[:0], self.value[:0]
+        check(self.lib.uttt_nn_stem_states(_p(states_dev), n, _p(self.stem_w), _p(self.stem_b), _p(self.buf[0]),
+                                           self._stream()))
+        return self._tower_heads(n, softmax)
+
     def _dev_plan(self, stream, n_dev):
         """The device-count forward's 32 conv argument tuples (fixed buffers and weights), built
         once per (stream, count): the per-round host cost is then one ctypes call per kernel."""

@@ -187,6 +187,133 @@ class SolvedLeaves:
         return self.counts()["skipped"]
 
 
+def parse_symmetry(spec):
+    """A symmetry setting -> None (off) or (mode, seed): spec is None / "off", "hashed", "average", a fixed
+    symmetry 0..7 (int or digit), or a (mode, seed) pair; a string may end in ":seed" (UTTT_SYMMETRY's form)."""
+    if spec is None:
+        return None
+    if isinstance(spec, tuple):
+        if len(spec) != 2:
+            raise ValueError(f"a symmetry pair is (mode, seed) (got {spec!r})")
+        mode = parse_symmetry(spec[0])
+        return None if mode is None else (mode[0], int(spec[1]))
+    seed = 0
+    if isinstance(spec, str):
+        spec, _, tail = spec.strip().partition(":")
+        if tail:
+            seed = int(tail, 0)
+        if spec in ("", "off"):
+            return None
+        if spec.isdigit():
+            spec = int(spec)
+    if spec in ("hashed", "average"):
+        return spec, seed
+    if isinstance(spec, (int, np.integer)) and not isinstance(spec, bool) and 0 <= int(spec) <= 7:
+        return int(spec), seed
+    raise ValueError(f"symmetry must be off, hashed, average or 0..7, with an optional :seed (got {spec!r})")
+
+
+def symmetry_from_env():
+    """UTTT_SYMMETRY = off (default) | hashed | average | 0..7, with an optional :seed, as parse_symmetry reads it."""
+    return parse_symmetry(os.environ.get("UTTT_SYMMETRY", "off"))
+
+
+def with_symmetry(evaluator, engine, symmetry):
+    """`evaluator` as it is (symmetry None / "off") or wrapped in SymmetricLeaves."""
+    sym = parse_symmetry(symmetry)
+    if sym is None:
+        return evaluator
+    return SymmetricLeaves(evaluator, engine, mode=sym[0], seed=sym[1])
+
+
+class SymmetricLeaves:
+    """Any evaluator that takes its leaves from the caller, seen through a symmetry of the square:
+    the round's pending leaves are transformed on the device (Engine.sym_pending_dev), `base` evaluates the
+    images, and the rows are mapped back to the leaves' own actions (Engine.sym_rows_dev; the value of a
+    position and of its image are the same). mode:
+
+      "hashed"   one symmetry per leaf, chosen by the playout key of the position's 243 input bits and `seed`
+                 (symmetry.hashed_symmetry): along a search path the network's errors decorrelate, at the cost
+                 of two small launches per round;
+      "average"  the mean over all eight, accumulated in f32 in the order g = 0..7 and multiplied by 0.125:
+                 eight evaluations per round;
+      0..7       that symmetry for every leaf.
+
+    A base with forward_device_states(states, n) (FusedNetworkEvaluator) gets the transformed states and
+    reads the count on the device: device_count is the base's and needs_input is False. Any other base is
+    called as base(x, n) with the wrapper's own NCHW buffer of the images and a host count (NetworkEvaluator,
+    arena.ModelEvaluator, HashEvaluator): device_count is False, and the base's one-call rounds (round_async,
+    round_move, cheap) are not exposed. A base that reads the engine's pending leaves itself would not see
+    the images and is refused with a TypeError: PlayoutEvaluator, SolvedLeaves (wrap the other way round:
+    SolvedLeaves(SymmetricLeaves(...)), the overlay last), another SymmetricLeaves, and any base asked for a
+    device count it could only serve from the engine's own leaves (HashEvaluator with a RoundCount).
+    One row per leaf: per-copy applies are out of scope, as for SolvedLeaves.
+
+    Cache rule: the result is a function of the position, the mode and the seed (given that `base` is one of
+    the position), so a search stays exact under the evaluation cache while they do not change.
+    SelfPlay.set_evaluator clears the table; a BatchedSearch user who changes the mode or the seed on a cached
+    engine calls Engine.cache_clear.
+
+    The engine's kernels launch on the engine's stream, which in BatchedSearch and SelfPlay is the stream the
+    evaluator runs on, so transform, evaluation and back-mapping are ordered. forward_kw (e.g. softmax=False)
+    is passed on to forward_device_states."""
+
+    def __init__(self, base, engine, mode="hashed", seed=0, **forward_kw):
+        if isinstance(mode, str) and mode not in ("hashed", "average"):
+            raise ValueError(f"mode must be 'hashed', 'average' or a symmetry 0..7 (got {mode!r})")
+        if not isinstance(mode, str):
+            if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or not 0 <= int(mode) <= 7:
+                raise ValueError(f"mode must be 'hashed', 'average' or a symmetry 0..7 (got {mode!r})")
+            mode = int(mode)
+        self._states_path = callable(getattr(base, "forward_device_states", None))
+        if isinstance(base, (PlayoutEvaluator, SolvedLeaves, SymmetricLeaves)) or \
+                (not self._states_path and not getattr(base, "needs_input", True)):
+            raise TypeError(f"{type(base).__name__} reads the engine's pending leaves itself and would not see "
+                            "the transformed ones: it cannot be wrapped in SymmetricLeaves")
+        self.base = base
+        self.engine = engine
+        self.mode = mode
+        self.seed = int(seed)
+        self.forward_kw = forward_kw
+        self.needs_input = False  # the wrapper builds the images' input itself, when the base reads one
+        self.device_count = self._states_path and bool(getattr(base, "device_count", False))
+        dev = torch.device("cuda", engine.device)
+        n = engine.max_trees
+        self.states = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+        self.sym = torch.zeros((n,), dtype=torch.int8, device=dev)
+        self.x = None if self._states_path else torch.zeros((n, 3, 9, 9), dtype=torch.float32, device=dev)
+        self.policy = torch.zeros((n, 81), dtype=torch.float32, device=dev)
+        self.value = torch.zeros((n, 1), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the fills, before the engine's stream writes into them
+
+    def _pass(self, n, mode, g_or_seed, accumulate, scale):
+        self.engine.sym_pending_dev(mode, g_or_seed, self.states, self.sym, self.x)
+        if self._states_path:
+            p, v = self.base.forward_device_states(self.states, n, **self.forward_kw)
+        else:
+            p, v = self.base(self.x, n)
+            p = p if p.dtype == torch.float32 and p.stride(1) == 1 else p.float().contiguous()
+            v = v if v.dtype == torch.float32 else v.float()
+        rows = len(p)
+        out_v = self.value[:rows] if v.dim() == 2 else self.value[:rows, 0]
+        self.engine.sym_rows_dev(self.sym, p, v, self.policy[:rows], out_v, accumulate, scale)
+
+    def __call__(self, x, n):
+        if isinstance(n, RoundCount) and not self.device_count:
+            raise TypeError(f"{type(self.base).__name__} could serve a device count only from the engine's own "
+                            "pending leaves: SymmetricLeaves calls it with a host count")
+        if self.mode == "average":
+            for g in range(8):
+                self._pass(n, "fixed", g, g > 0, 0.125 if g == 7 else 1.0)
+        elif self.mode == "hashed":
+            self._pass(n, "hashed", self.seed, False, 1.0)
+        else:
+            self._pass(n, "fixed", self.mode, False, 1.0)
+        if isinstance(n, RoundCount):
+            return self.policy, self.value
+        return self.policy[:n], self.value[:n]
+
+
 class NetworkEvaluator:
     """DualNetwork (or any model with its call signature) on the engine's device."""
 
@@ -201,13 +328,15 @@ class NetworkEvaluator:
         return p[:n].float(), v[:n].float()
 
 
-def model_evaluator_factory(model, kind=None):
+def model_evaluator_factory(model, kind=None, symmetry=None):
     """make(engine) -> evaluator for a model: the fused HIP evaluator for a DualNetwork (the
-    drop-ins' default, nnfast.evaluator_kind), else the model called on the engine's NCHW batch."""
+    drop-ins' default, nnfast.evaluator_kind), else the model called on the engine's NCHW batch.
+    symmetry (parse_symmetry's forms; default off): the evaluator wrapped in SymmetricLeaves."""
     from .nnfast import FusedNetworkEvaluator, evaluator_kind
+    parse_symmetry(symmetry)  # a bad setting fails here, not at the first engine
     if evaluator_kind(model, kind) == "fused":
-        return lambda eng: FusedNetworkEvaluator(model, eng)
-    return lambda eng: NetworkEvaluator(model, eng.max_trees)
+        return lambda eng: with_symmetry(FusedNetworkEvaluator(model, eng), eng, symmetry)
+    return lambda eng: with_symmetry(NetworkEvaluator(model, eng.max_trees), eng, symmetry)
 
 
 class BatchedSearch:
@@ -301,7 +430,7 @@ class SelfPlay:
     last waves on the GPU. Records are unchanged (each game depends only on its id)."""
 
     def __init__(self, slots, evaluate_count=50, batch_size=8, temperature=1.0, device=None, evaluator=None,
-                 model=None, cache_log2=None, cache_clear_every=0, lanes=1, evaluator_kind=None):
+                 model=None, cache_log2=None, cache_clear_every=0, lanes=1, evaluator_kind=None, symmetry=None):
         if lanes < 1 or slots % lanes:
             raise ValueError("slots must be a positive multiple of lanes")
         per = slots // lanes
@@ -320,7 +449,9 @@ class SelfPlay:
         self.batch_size = batch_size
         self.temperature = temperature
         if evaluator is None and model is not None:
-            self.set_evaluator(model_evaluator_factory(model, evaluator_kind))
+            self.set_evaluator(model_evaluator_factory(model, evaluator_kind, symmetry))
+        elif parse_symmetry(symmetry) is not None:
+            raise ValueError("symmetry applies to the model's evaluator: wrap your own in SymmetricLeaves")
         elif evaluator is None:
             self.set_evaluator(HashEvaluator)
         else:
@@ -709,4 +840,5 @@ def history_from_records(records):
 
 
 __all__ = ["BatchedSearch", "SelfPlay", "HashEvaluator", "PlayoutEvaluator", "NetworkEvaluator", "history_from_records",
-           "initial_states", "model_evaluator_factory", "default_lanes"]
+           "initial_states", "model_evaluator_factory", "default_lanes", "SymmetricLeaves", "parse_symmetry",
+           "symmetry_from_env", "with_symmetry"]

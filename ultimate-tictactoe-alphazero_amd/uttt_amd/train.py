@@ -83,6 +83,32 @@ def batches(n, batch_size, epoch, seed):
     return [perm[i:i + batch_size] for i in range(0, n, batch_size)]
 
 
+class EpochAugmenter:
+    """Symmetry augmentation of the resident dataset (train_network(augment=True)). The pristine
+    inputs and policies x0, p0 are kept; at the start of each epoch one of the eight symmetries of the square is
+    drawn per sample from a generator seeded by (seed, epoch), the same on every rank as `batches` is, and
+    symmetry.transform_inputs(x0, sym) / transform_policy(p0, sym) are written in place into x and p, the
+    tensors the steps index: a captured graph's addresses stay valid and the step code is untouched. Values
+    are invariant. sym: the current epoch's draw (a host int64 tensor)."""
+
+    def __init__(self, x, p, seed):
+        from . import symmetry
+        self.symmetry = symmetry
+        self.x, self.p, self.seed = x, p, int(seed)
+        self.x0, self.p0 = x.clone(), p.clone()
+        self.sym = None
+
+    def draw(self, epoch):
+        g = torch.Generator().manual_seed((1 << 40) + self.seed * 1000003 + epoch)
+        return torch.randint(0, 8, (len(self.x0),), generator=g)
+
+    def epoch(self, epoch):
+        self.sym = self.draw(epoch)
+        s = self.sym.to(self.x.device)
+        self.symmetry.transform_inputs(self.x0, s, out=self.x)
+        self.symmetry.transform_policy(self.p0, s, out=self.p)
+
+
 def local_slice(idx, rank, world):
     """Rank's contiguous share of one global batch (sizes differ by at most one)."""
     base, extra = divmod(len(idx), world)
@@ -336,8 +362,10 @@ def _use_graph(graph, device, world):
 
 def train_network(model, history, epochs=RN_EPOCHS, batch_size=BATCH_SIZE, device=None, seed=0, lr=0.001,
                   log=print, sync_bn=None, graph=None, channels_last=False, precision=None, tune=None, adam=None,
-                  dp=None):
+                  dp=None, augment=False):
     """Train `model` (a DualNetwork) on `history` in place; returns the per-epoch mean losses.
+    augment (default off): every epoch trains on a fresh random symmetry image of each sample (EpochAugmenter),
+    whichever step form runs.
     In a torch.distributed job every rank calls this with the same history and seed.
     graph (default on for one GPU; UTTT_TRAIN_GRAPH=0 disables): replay the step as a HIP graph
     (GraphedStep); the eager loop otherwise.
@@ -361,14 +389,15 @@ def train_network(model, history, epochs=RN_EPOCHS, batch_size=BATCH_SIZE, devic
         dp = os.environ.get("UTTT_TRAIN_DP", "ddp")
     if dp not in ("flat", "ddp"):
         raise ValueError("dp must be 'flat' or 'ddp'")
+    aug = EpochAugmenter(x, p, seed) if augment else None
     if _use_graph(graph, device, world):
         return _train_graphed(model, x, p, v, epochs, batch_size, device, seed, lr, log, channels_last, precision, tune,
-                              adam)
+                              adam, aug)
     if world > 1 and dp == "flat":
         if precision != "fp32":
             raise ValueError("the data-parallel step trains in fp32")
         return _train_dp_flat(model, x, p, v, epochs, batch_size, device, seed, lr, log,
-                              graph=graph is not False and device.type == "cuda", tune=tune)
+                              graph=graph is not False and device.type == "cuda", tune=tune, aug=aug)
     if precision != "fp32":
         raise ValueError("precision other than fp32 needs the graph step (one GPU)")
     net = prepare(model, device, sync_bn)
@@ -380,6 +409,8 @@ def train_network(model, history, epochs=RN_EPOCHS, batch_size=BATCH_SIZE, devic
     net.train()
     losses = []
     for epoch in range(epochs):
+        if aug is not None:
+            aug.epoch(epoch)
         total = torch.zeros((), device=device)
         nb = 0
         for idx in batches(len(x), batch_size, epoch, seed):
@@ -397,7 +428,7 @@ def train_network(model, history, epochs=RN_EPOCHS, batch_size=BATCH_SIZE, devic
     return losses
 
 
-def _train_dp_flat(model, x, p, v, epochs, batch_size, device, seed, lr, log, graph=True, tune=False):
+def _train_dp_flat(model, x, p, v, epochs, batch_size, device, seed, lr, log, graph=True, tune=False, aug=None):
     """The data-parallel loop on DPGraphedStep (see there): every rank draws the epoch's permutation from
     the same generator and steps on its slice of each global batch."""
     rank, world = _world()
@@ -416,6 +447,8 @@ def _train_dp_flat(model, x, p, v, epochs, batch_size, device, seed, lr, log, gr
     step = DPGraphedStep(net, opt, x, p, v, len(full), len(full) / batch_size, graph=graph, tune=tune)
     losses = []
     for epoch in range(epochs):
+        if aug is not None:
+            aug.epoch(epoch)
         f = lr * lr_lambda(epoch)
         if lr_t is not None:
             lr_t.fill_(f)
@@ -441,7 +474,7 @@ def _train_dp_flat(model, x, p, v, epochs, batch_size, device, seed, lr, log, gr
 
 
 def _train_graphed(model, x, p, v, epochs, batch_size, device, seed, lr, log, channels_last, precision="fp32",
-                   tune=False, adam="fused"):
+                   tune=False, adam="fused", aug=None):
     net = model.to(device)
     if channels_last:
         net = net.to(memory_format=torch.channels_last)
@@ -460,6 +493,8 @@ def _train_graphed(model, x, p, v, epochs, batch_size, device, seed, lr, log, ch
     step = GraphedStep(net, opt, x, p, v, batch_size, channels_last, precision, tune)
     losses = []
     for epoch in range(epochs):
+        if aug is not None:
+            aug.epoch(epoch)
         lr_t.fill_(lr * lr_lambda(epoch))
         step.loss_sum.zero_()
         idxs = batches(len(x), batch_size, epoch, seed)
@@ -476,5 +511,5 @@ def _train_graphed(model, x, p, v, epochs, batch_size, device, seed, lr, log, ch
     return losses
 
 
-__all__ = ["BATCH_SIZE", "DPGraphedStep", "F16_LOSS_SCALE", "GraphedStep", "PRECISIONS", "RN_EPOCHS", "batches", "history_arrays", "local_slice", "lr_lambda",
+__all__ = ["BATCH_SIZE", "DPGraphedStep", "EpochAugmenter", "F16_LOSS_SCALE", "GraphedStep", "PRECISIONS", "RN_EPOCHS", "batches", "history_arrays", "local_slice", "lr_lambda",
            "policy_loss_fn", "prepare", "train_network", "train_step"]
