@@ -154,6 +154,15 @@ int uttt_states_transform_host(const uttt_state_t *states, int64_t n, const int8
 /* The hashed choice: sym[i] = the top three bits of the playout key (csrc/uttt_playout.h) of state i's 243
  * network-input bits and `seed`: a function of the stones, the legal moves and the seed alone. */
 int uttt_states_symmetry_host(const uttt_state_t *states, int64_t n, uint64_t seed, int8_t *sym);
+/* Dirichlet noise on root priors (csrc/uttt_noise.h): for n roots whose priors are uniform, with
+ * L legal moves each, eta ~ Dirichlet(alpha) over the moves in ascending action order and the mixed priors
+ * fmaf(epsilon, eta, (1 - epsilon) / L): row r, rank i at [r * 81 + i], entries at ranks >= L left untouched;
+ * either output may be NULL. Row r is a function of (seed, stream[r], ply[r], L) alone: what
+ * uttt_engine_set_root_noise makes the engine write, where stream is the global game id and ply the game's ply
+ * in self-play, and the tree index and 0 in a plain search. Pure CPU. UTTT_ERR_ARG for epsilon outside [0, 1]
+ * or alpha outside [1/32, 32]. */
+int uttt_root_noise_host(const uttt_state_t *states, int64_t n, const int64_t *stream, const int32_t *ply,
+                         float epsilon, float alpha, uint64_t seed, float *eta, float *priors);
 
 /* --------------------------------------------------------------- engine --- */
 typedef struct uttt_engine uttt_engine_t;
@@ -360,6 +369,18 @@ int uttt_search_root_visits(uttt_engine_t *eng, int32_t *visits, int32_t *n_lega
  * max for temperature 0, else boltzman; row stride 81. */
 int uttt_search_scores(uttt_engine_t *eng, float temperature, float *scores, int32_t *n_legal);
 
+/* The priors P of the root's children (legal order, row stride 81, zeros past |legal|) and |legal| per tree,
+ * any time after the search began: 1.0f / |legal| unless root noise is on. Either output may be NULL. */
+int uttt_search_root_priors(uttt_engine_t *eng, float *priors, int32_t *n_legal);
+/* Root exploration noise: with epsilon > 0 every root built from then on by uttt_search_begin,
+ * uttt_search_begin_mode(UTTT_SEMANTICS_CPP) or a self-play move begin (blocking or _async) gets the priors
+ * uttt_root_noise_host describes, written by one extra launch (k_root_noise) behind the one that builds the
+ * roots. epsilon 0 (the default) is off: no launch, today's priors. While it is on,
+ * uttt_search_begin_mode(UTTT_SEMANTICS_PY) and uttt_search1_begin return UTTT_ERR_ARG (a py root's priors come
+ * from its first flush; the resident one-tree search builds its root inside its own kernel). UTTT_ERR_ARG for
+ * epsilon outside [0, 1] or alpha outside [1/32, 32] (alpha is checked even when epsilon is 0). */
+int uttt_engine_set_root_noise(uttt_engine_t *eng, float epsilon, float alpha, uint64_t seed);
+
 /* -------------------------------------------------------------- self-play --- */
 /* Self-play of games [game_begin, game_end) (self_play_cpp.py:34-130), each
  * game g with its own numpy-legacy MT19937 seeded seed_base + g (=
@@ -377,6 +398,13 @@ int uttt_selfplay_move_begin(uttt_engine_t *eng, int32_t *n_live);
  * ended games get their values (self_play_cpp.py:95-99) and are written to
  * the arena; free slots take the next game. *n_finished = games in the arena. */
 int uttt_selfplay_move_end(uttt_engine_t *eng, int64_t *n_finished);
+/* A temperature schedule for self-play: a move made at ply < plies uses uttt_selfplay_begin's temperature, a
+ * later one late_temperature (0 = the most visited move), for the sampled move and the recorded policy target
+ * alike. A setting of the engine: call it before or after uttt_selfplay_begin, between moves (UTTT_ERR_ORDER
+ * between a self-play move's begin and its end); it holds for every move end enqueued afterwards and across
+ * later uttt_selfplay_begin calls. The default, plies = INT32_MAX, is one temperature for the whole game.
+ * UTTT_ERR_ARG for plies < 0 or a late_temperature that is negative or not finite. */
+int uttt_selfplay_set_temperature_schedule(uttt_engine_t *eng, int32_t plies, float late_temperature);
 /* numpy-legacy MT19937 state of a slot's current game (624 words + position),
  * so a caller can run a game on numpy's global RandomState and continue it
  * afterwards (self_play_cpp.play draws from np.random, self_play_cpp.py:86). */
@@ -427,7 +455,7 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
 /* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve,
- * 17 solve_leaves, 18 sym_leaves, 19 sym_rows.
+ * 17 solve_leaves, 18 sym_leaves, 19 sym_rows, 20 root_noise.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

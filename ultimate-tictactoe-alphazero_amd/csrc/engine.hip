@@ -27,6 +27,8 @@
 //   cache.h   EvalCache: probe, lookup, insert
 //   expand.h  legal masks, f32 sums, expand_backup, init_root, k_begin
 //   symmetry.h  k_sym_leaves, k_sym_rows: the pending leaves through a symmetry, the rows mapped back
+// and, behind the last kernel defined here:
+//   noise.h   k_root_noise, k_root_priors: Dirichlet noise mixed into the roots' priors, the priors read back
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -41,6 +43,7 @@
 #include "engine_mem.h"
 #include "uttt_bits.h"
 #include "uttt_engine.h"
+#include "uttt_noise.h"
 #include "uttt_playout.h"
 #include "uttt_solve.h"
 #include "uttt_sym.h"
@@ -1644,6 +1647,10 @@ struct SelfPlay {
     uint32_t seed_base;
     float temperature;
     int32_t slots;
+    // the temperature schedule (uttt_selfplay_set_temperature_schedule): `temperature` while Slot.ply < temp_plies,
+    // late_temperature from then on; INT32_MAX: one temperature for the whole game
+    int32_t temp_plies = INT32_MAX;
+    float late_temperature = 0.0f;
 };
 
 // numpy legacy RandomState: init_genrand(seed) (mt19937_seed), genrand_int32
@@ -1765,9 +1772,10 @@ __global__ __launch_bounds__(kBlock) void k_move_end(Pool pool, SelfPlay sp, con
     }
     const double u = ((double)(w1 >> 5) * 67108864.0 + (double)(w2 >> 6)) / 9007199254740992.0;
     const int ply = sl.ply;
+    const float temperature = ply < sp.temp_plies ? sp.temperature : sp.late_temperature;  // (wave-uniform)
     // root visit counts (uttt_mcts.cpp:177-192, as root_scores): entry i in lane i / i - 64 (loaded above)
     double x0, x1;
-    if (sp.temperature == 0.0f) {
+    if (temperature == 0.0f) {
         // one-hot first max: the largest count, then the lowest index holding it (counts < 2^24, so
         // the f32 compares of the reference order them as the integers do)
         int kk = max(h0 ? (n0 << 8) | (255 - lane) : -1, h1 ? (n1 << 8) | (255 - 64 - lane) : -1);
@@ -1777,7 +1785,7 @@ __global__ __launch_bounds__(kBlock) void k_move_end(Pool pool, SelfPlay sp, con
         x0 = (h0 && lane == mi) ? 1.0 : 0.0;
         x1 = (h1 && lane + 64 == mi) ? 1.0 : 0.0;
     } else {
-        const double y = (double)(1.0f / sp.temperature);  // glibc powf: double pow, one rounding
+        const double y = (double)(1.0f / temperature);  // glibc powf: double pow, one rounding
         float v0 = 0.0f, v1 = 0.0f, sum = 0.0f;
         if (y == 1.0) {
             // pow(x, 1) == x exactly (IEEE 754); a sum of integers below 2^24 is exact in f32 in
@@ -2117,6 +2125,14 @@ __global__ void k_hwc(const uttt_state_t *st, int64_t n, float *out) {
 
 }  // namespace uttt
 
+// Root noise (k_root_noise, k_root_priors): the last kernels of the translation unit, behind every kernel of the
+// round loop and the move end, whose places in the code object they leave as they were
+#include "engine/noise.h"
+namespace uttt {
+static_assert(offsetof(Slot, ply) == offsetof(Slot, game) + offsetof(NoiseKey, ply) && offsetof(NoiseKey, stream) == 0,
+              "k_root_noise reads a slot's game and ply as one NoiseKey");
+}  // namespace uttt
+
 // ============================================================== host side ==
 using namespace uttt;
 
@@ -2234,6 +2250,9 @@ struct uttt_engine {
     bool cache_owner = true;  // false: the table belongs to another engine (uttt_engine_share_cache)
     int64_t moves = 0;
     DevBuf<unsigned long long> d_cache_ctr;
+    // root noise (uttt_engine_set_root_noise): off while noise_eps is 0
+    float noise_eps = 0.0f, noise_alpha = 1.0f;
+    uint64_t noise_seed = 0;
     // telemetry
     bool timing = false;
     DevBuf<unsigned long long> d_bytes;  // [kKernelCount]
@@ -2556,17 +2575,36 @@ static int begin_with_semantics(uttt_engine *e, const char *fn, const uttt_state
     return UTTT_OK;
 }
 
+// Root noise, when it is on, behind the k_begin that built the roots (keys: the self-play slots' NoiseKey words, or
+// nullptr for a plain search)
+static void launch_root_noise(uttt_engine *e, const char *keys, int key_stride) {
+    if (!(e->noise_eps > 0.0f)) return;
+    timed_launch(e, kKRootNoise, k_root_noise, dim3(grid_waves(e->tr.n_trees)), dim3(kBlock), e->pool, e->tr, keys,
+                 key_stride, e->noise_eps, e->noise_alpha, e->noise_seed);
+}
+// What has no root priors to mix noise into when a search begins (fn) refuses an engine with noise on
+static int refuse_root_noise(uttt_engine *e, const char *fn, const char *why) {
+    if (!e || !(e->noise_eps > 0.0f)) return UTTT_OK;
+    set_error("%s: root noise is on (uttt_engine_set_root_noise) and %s", fn, why);
+    return UTTT_ERR_ARG;
+}
+
 int uttt_search_begin(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch) {
     return uttt_search_begin_mode(e, roots, n_trees, sims, batch, UTTT_SEMANTICS_CPP);
 }
 
 int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch,
                            int32_t semantics) {
+    if (semantics == UTTT_SEMANTICS_PY)
+        if (int rc = refuse_root_noise(e, "uttt_search_begin_mode",
+                                       "a py root takes its priors from its first flush: use UTTT_SEMANTICS_CPP"))
+            return rc;
     if (int rc = begin_with_semantics(e, "uttt_search_begin_mode", roots, n_trees, sims, batch, semantics)) return rc;
     HIP_TRY(hipMemcpyAsync(e->tr.leaf, roots, sizeof(uttt_state_t) * n_trees, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_begin, dim3(grid_waves(n_trees)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
                        (const char *)e->tr.leaf, (int)sizeof(uttt_state_t), (const int32_t *)nullptr,
                        (unsigned long long *)nullptr);
+    launch_root_noise(e, nullptr, 0);
     return check_launch();
 }
 
@@ -2754,6 +2792,9 @@ static int search1_launch(uttt_engine *e, int32_t resume) {
 
 int uttt_search1_begin(uttt_engine_t *e, const uttt_state_t *root, int32_t sims, int32_t batch, int32_t semantics,
                        float temperature) {
+    if (int rc = refuse_root_noise(e, "uttt_search1_begin",
+                                   "the resident one-tree search builds its root itself: use uttt_search_begin"))
+        return rc;
     // (search_begin_common: a resident wave left by an unfinished search exits first)
     if (int rc = begin_with_semantics(e, "uttt_search1_begin", root, 1, sims, batch, semantics)) return rc;
     const int32_t need = e->tr.batch > 16 ? e->tr.batch : 16;  // rows per flush: 1 or k <= batch
@@ -3367,7 +3408,49 @@ int uttt_search_scores(uttt_engine_t *e, float temperature, float *scores, int32
     return UTTT_OK;
 }
 
+int uttt_search_root_priors(uttt_engine_t *e, float *priors, int32_t *n_legal) {
+    int rc = root_results_ready(e);
+    if (rc) return rc;
+    const int n = e->tr.n_trees;
+    if (n <= 0) {
+        set_error("uttt_search_root_priors: no search has begun");
+        return UTTT_ERR_ORDER;
+    }
+    hipLaunchKernelGGL(k_root_priors, dim3((n * 81 + 255) / 256), dim3(256), 0, e->stream, e->pool, e->tr,
+                       e->d_scores.get(), e->d_nlegal.get());
+    if ((rc = check_launch())) return rc;
+    if (priors) HIP_TRY(hipMemcpyAsync(priors, e->d_scores, sizeof(float) * 81 * n, hipMemcpyDeviceToHost, e->stream));
+    if (n_legal) HIP_TRY(hipMemcpyAsync(n_legal, e->d_nlegal, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return UTTT_OK;
+}
+
+int uttt_engine_set_root_noise(uttt_engine_t *e, float epsilon, float alpha, uint64_t seed) {
+    if (!e) return UTTT_ERR_ARG;
+    if (int rc = noise_check_args("uttt_engine_set_root_noise", epsilon, alpha)) return rc;
+    e->noise_eps = epsilon;
+    e->noise_alpha = alpha;
+    e->noise_seed = seed;
+    return UTTT_OK;
+}
+
 // ----------------------------------------------------------- self-play API --
+int uttt_selfplay_set_temperature_schedule(uttt_engine_t *e, int32_t plies, float late_temperature) {
+    if (!e) return UTTT_ERR_ARG;
+    if (plies < 0 || !(late_temperature >= 0.0f && late_temperature <= 3.0e38f)) {
+        set_error("uttt_selfplay_set_temperature_schedule: plies must be >= 0 and late_temperature finite and >= 0 "
+                  "(got %d, %g)", plies, (double)late_temperature);
+        return UTTT_ERR_ARG;
+    }
+    if (e->selfplay && e->phase != 0) {
+        set_error("uttt_selfplay_set_temperature_schedule: a move is in flight (call it between moves)");
+        return UTTT_ERR_ORDER;
+    }
+    e->sp.temp_plies = plies;
+    e->sp.late_temperature = late_temperature;
+    return UTTT_OK;
+}
+
 int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, uint32_t seed_base, float temperature,
                         int32_t sims, int32_t batch, int64_t arena_plies) {
     if (!e || game_end < game_begin || game_begin < 0 || arena_plies <= 0) {
@@ -3437,6 +3520,7 @@ static int launch_move_begin(uttt_engine *e) {
     e->moves++;
     hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
                        (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err.get());
+    launch_root_noise(e, (const char *)e->sp.slot + offsetof(Slot, game), (int)sizeof(Slot));
     if (int rc = check_launch()) return rc;
     e->phase = 1;
     e->n_pending = 0;

@@ -9,6 +9,7 @@
 
 #include "uttt_bits.h"
 #include "uttt_engine.h"
+#include "uttt_noise.h"
 #include "uttt_playout.h"
 #include "uttt_solve.h"
 #include "uttt_sym.h"
@@ -42,6 +43,19 @@ int solve_check_args(const char *who, const uttt_state_t *states, int64_t n, int
             set_error("active_board must be -1..8 (state %lld has %d)", (long long)i, states[i].active);
             return UTTT_ERR_ARG;
         }
+    }
+    return UTTT_OK;
+}
+
+// The argument checks uttt_root_noise_host and uttt_engine_set_root_noise share.
+int noise_check_args(const char *who, float epsilon, float alpha) {
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) {
+        set_error("%s: epsilon must be in [0, 1] (got %g)", who, (double)epsilon);
+        return UTTT_ERR_ARG;
+    }
+    if (!(alpha >= kNoiseAlphaMin && alpha <= kNoiseAlphaMax)) {
+        set_error("%s: alpha must be in [1/32, 32] (got %g)", who, (double)alpha);
+        return UTTT_ERR_ARG;
     }
     return UTTT_OK;
 }
@@ -408,6 +422,24 @@ int uttt_states_symmetry_host(const uttt_state_t *states, int64_t n, uint64_t se
         uint64_t w[4];
         input_words(states[i], w);
         sym[i] = (int8_t)sym_of_key(w, seed);
+    }
+    return UTTT_OK;
+}
+
+int uttt_root_noise_host(const uttt_state_t *states, int64_t n, const int64_t *stream, const int32_t *ply, float epsilon,
+                         float alpha, uint64_t seed, float *eta, float *priors) {
+    // uttt_noise.h for n roots with uniform priors; what k_root_noise writes into the roots' child blocks.
+    if (int rc = noise_check_args("uttt_root_noise_host", epsilon, alpha)) return rc;
+    if (int rc = check_sym_states("uttt_root_noise_host", states, n, stream, ply)) return rc;
+    for (int64_t r = 0; r < n; ++r) {
+        const int L = (int)legal_count(states[r]);
+        float row[81];
+        noise_eta_row(alpha, noise_key(seed, (uint64_t)stream[r], (uint32_t)ply[r]), L, row);
+        const float up = L ? 1.0f / (float)L : 0.0f;
+        for (int i = 0; i < L; ++i) {
+            if (eta) eta[r * 81 + i] = row[i];
+            if (priors) priors[r * 81 + i] = noise_mix(epsilon, row[i], up);
+        }
     }
     return UTTT_OK;
 }

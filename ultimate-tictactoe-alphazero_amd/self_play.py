@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import uttt_cpp  # noqa: E402
 from pv_mcts import pv_mcts_scores  # noqa: E402
 from uttt_amd import arena  # noqa: E402
+from uttt_amd.noise import root_noise_from_env, temperature_plies_from_env  # noqa: E402
 from uttt_amd.selfplay import symmetry_from_env  # noqa: E402
 from uttt_amd.model import DN_INPUT_SHAPE, DualNetwork  # noqa: E402,F401
 
@@ -73,8 +74,14 @@ def self_play():
         print("\rSelfPlay {}/{}".format(done, total), end="")
 
     # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed: leaves seen through a symmetry
+    # UTTT_TEMPERATURE_PLIES = n[,late]: moves from ply n on at temperature late (default 0)
+    # UTTT_ROOT_NOISE: the pv_mcts.py search takes a root's priors from its first flush, so there is nothing to mix
+    # noise into; self_play_cpp.py has it
+    if root_noise_from_env() is not None:
+        raise ValueError("UTTT_ROOT_NOISE needs the cpp search: run self_play_cpp.py (this script searches as pv_mcts.py)")
+    plies, late = temperature_plies_from_env()
     games = arena.self_play_py(model, SP_GAME_COUNT, seed_base, SP_TEMPERATURE, progress=progress,
-                               symmetry=symmetry_from_env())
+                               symmetry=symmetry_from_env(), temperature_plies=plies, late_temperature=late)
     print("")
     history = [rec for g in games for rec in g]
     write_data(history)

@@ -40,6 +40,7 @@ except ImportError:
 from uttt_amd.model import DualNetwork  # noqa: E402
 from uttt_amd.distributed import broadcast_int, init_from_env, self_play_sharded  # noqa: E402
 from uttt_amd.history import write_history_file  # noqa: E402
+from uttt_amd.noise import root_noise_from_env, temperature_plies_from_env  # noqa: E402
 from uttt_amd.selfplay import SelfPlay, default_lanes, history_from_records, symmetry_from_env  # noqa: E402
 
 SP_GAME_COUNT = 500
@@ -57,14 +58,23 @@ def _fingerprint(model):
     return tuple((t.data_ptr(), t._version) for t in model.state_dict().values())
 
 
+def _exploration():
+    """SelfPlay's exploration arguments from the environment (unset: off): UTTT_ROOT_NOISE = "eps,alpha[,seed]",
+    Dirichlet noise on every move's root priors; UTTT_TEMPERATURE_PLIES = "n[,late]", moves from ply n on at
+    temperature late (default 0)."""
+    plies, late = temperature_plies_from_env()
+    return dict(root_noise=root_noise_from_env(), temperature_plies=plies, late_temperature=late)
+
+
 def _runner(model, slots):
     """One cached single-game runner per model (rebuilt when its weights change)."""
     sym = symmetry_from_env()  # UTTT_SYMMETRY = off (default) | hashed | average | 0..7, optional :seed
-    key = (id(model), slots, _fingerprint(model), sym)
+    explore = _exploration()
+    key = (id(model), slots, _fingerprint(model), sym, tuple(sorted(explore.items())))
     r = _single.get("runner") if _single.get("key") == key else None
     if r is None:
         _single.clear()
-        r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, model=model, symmetry=sym)
+        r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, model=model, symmetry=sym, **explore)
         _single.update(key=key, runner=r)
     return r
 
@@ -136,11 +146,11 @@ def self_play(use_cpp=True, n_games=None, slots=None, seed_base=None, model_path
     if world > 1:
         recs = self_play_sharded(model, n_games, slots, seed_base, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE,
                                  SP_TEMPERATURE, lanes=lanes, progress=progress, timings=LAST_TIMINGS,
-                                 symmetry=symmetry_from_env())
+                                 symmetry=symmetry_from_env(), **_exploration())
     else:
         n_lanes = default_lanes(slots) if lanes is None else lanes
         r = SelfPlay(slots, PV_EVALUATE_COUNT, MCTS_BATCH_SIZE, SP_TEMPERATURE, device=dev.index, model=model,
-                     lanes=n_lanes, symmetry=symmetry_from_env())
+                     lanes=n_lanes, symmetry=symmetry_from_env(), **_exploration())
         LAST_TIMINGS["setup_s"] = time.perf_counter() - t0
         LAST_TIMINGS["games_s"] = r.run(0, n_games, seed_base, progress)
         LAST_TIMINGS["sims"] = r.sims

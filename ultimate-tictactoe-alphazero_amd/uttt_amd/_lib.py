@@ -18,7 +18,7 @@ ERRORS = {-1: "UTTT_ERR_ARG", -2: "UTTT_ERR_HIP", -3: "UTTT_ERR_CAPACITY", -4: "
           -5: "UTTT_ERR_NODEVICE", -6: "UTTT_ERR_NONFINITE"}
 
 KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15, "solve": 16,
-           "solve_leaves": 17, "sym_leaves": 18, "sym_rows": 19,
+           "solve_leaves": 17, "sym_leaves": 18, "sym_rows": 19, "root_noise": 20,
            # select latency counters (their value is in "bytes"; no launches)
            "select_levels": 6, "select_trees": 7, "select_max_levels_sum": 9,
            "select_trips": 10, "select_max_trips_sum": 12}
@@ -72,6 +72,7 @@ SIGNATURES = {
     "uttt_sym_inverse": (ctypes.c_int, [_I32]),
     "uttt_states_transform_host": (ctypes.c_int, [_SP, _I64, _I8P, _SP]),
     "uttt_states_symmetry_host": (ctypes.c_int, [_SP, _I64, _U64, _I8P]),
+    "uttt_root_noise_host": (ctypes.c_int, [_SP, _I64, _I64P, _I32P, _F32, _F32, _U64, _F32P, _F32P]),
     "uttt_sym_pending_dev": (ctypes.c_int, [_P, _I32, _U64, _P, _P, _P]),
     "uttt_sym_rows_dev": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _F32]),
     "uttt_engine_create": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_P)]),
@@ -106,6 +107,9 @@ SIGNATURES = {
     "uttt_search_apply_host": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int32]),
     "uttt_search_root_visits": (ctypes.c_int, [_P, _I32P, _I32P]),
     "uttt_search_scores": (ctypes.c_int, [_P, _F32, _F32P, _I32P]),
+    "uttt_search_root_priors": (ctypes.c_int, [_P, _F32P, _I32P]),
+    "uttt_engine_set_root_noise": (ctypes.c_int, [_P, _F32, _F32, _U64]),
+    "uttt_selfplay_set_temperature_schedule": (ctypes.c_int, [_P, _I32, _F32]),
     "uttt_selfplay_begin": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_uint32, _F32, _I32, _I32, _I64]),
     "uttt_selfplay_move_begin": (ctypes.c_int, [_P, _I32P]),
     "uttt_selfplay_move_end": (ctypes.c_int, [_P, _I64P]),

@@ -187,11 +187,12 @@ def first_player_value(state):
 
 
 def self_play_py(model, game_count, seed_base=0, temperature=1.0, evaluate_count=50, batch_size=8, device=None,
-                 make_evaluator=None, progress=None, symmetry=None):
+                 make_evaluator=None, progress=None, symmetry=None, temperature_plies=None, late_temperature=0.0):
     """self_play.py:66-99 (the Python self-play: pv_mcts.py searches) for game_count games at once.
     Game g draws from RandomState(seed_base + g) (= play(model) after np.random.seed(seed_base + g)).
     Returns one history per game: [input (9,9,3) float64, policies (81 Python floats, 0 for
-    illegal actions), value (first_player_value at ply 0, then alternating)]."""
+    illegal actions), value (first_player_value at ply 0, then alternating)]. temperature_plies (default off):
+    moves from that ply on use late_temperature."""
     import uttt_cpp
     search = PvMcts(game_count, evaluate_count, device)
     ev = make_evaluator(model, search.engine) if make_evaluator else \
@@ -207,7 +208,8 @@ def self_play_py(model, game_count, seed_base=0, temperature=1.0, evaluate_count
         for g, v in zip(live, vis):
             st = states[g]
             legal = st.legal_actions()
-            scores = scores_from_visits(v, temperature)
+            late = temperature_plies is not None and len(hist[g]) >= temperature_plies
+            scores = scores_from_visits(v, late_temperature if late else temperature)
             policies = [0] * 81
             for action, policy in zip(legal, scores):
                 policies[action] = policy

@@ -344,6 +344,28 @@ class Engine:
         check(self.lib.uttt_search_root_visits(self.h, ptr(v, ctypes.c_int32), ptr(L, ctypes.c_int32)))
         return v, L
 
+    def root_priors(self):
+        """(priors, n_legal): the root children's P in legal order, (n_trees, 81) f32 with zeros past n_legal
+        (uttt_search_root_priors): 1.0f / n_legal unless root noise is on."""
+        p = np.zeros((self.n_trees, 81), np.float32)
+        L = np.zeros(self.n_trees, np.int32)
+        check(self.lib.uttt_search_root_priors(self.h, ptr(p, ctypes.c_float), ptr(L, ctypes.c_int32)))
+        return p, L
+
+    def set_root_noise(self, epsilon, alpha=0.3, seed=0):
+        """Dirichlet(alpha) noise mixed into every root's priors with weight epsilon from the next search_begin
+        ("cpp" semantics) or self-play move on (uttt_engine_set_root_noise; noise.root_noise_host gives the same
+        rows on the CPU). epsilon 0 turns it off."""
+        check(self.lib.uttt_engine_set_root_noise(self.h, float(epsilon), float(alpha),
+                                                  ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+
+    def set_temperature_schedule(self, plies=None, late_temperature=0.0):
+        """Self-play moves at ply >= plies use late_temperature instead of selfplay_begin's temperature
+        (uttt_selfplay_set_temperature_schedule; between moves, before or after selfplay_begin). plies None:
+        one temperature for the whole game."""
+        check(self.lib.uttt_selfplay_set_temperature_schedule(self.h, 0x7FFFFFFF if plies is None else int(plies),
+                                                              float(late_temperature)))
+
     def scores(self, temperature):
         s = np.zeros((self.n_trees, 81), np.float32)
         L = np.zeros(self.n_trees, np.int32)

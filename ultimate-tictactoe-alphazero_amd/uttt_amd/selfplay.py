@@ -430,7 +430,14 @@ class SelfPlay:
     last waves on the GPU. Records are unchanged (each game depends only on its id)."""
 
     def __init__(self, slots, evaluate_count=50, batch_size=8, temperature=1.0, device=None, evaluator=None,
-                 model=None, cache_log2=None, cache_clear_every=0, lanes=1, evaluator_kind=None, symmetry=None):
+                 model=None, cache_log2=None, cache_clear_every=0, lanes=1, evaluator_kind=None, symmetry=None,
+                 root_noise=None, temperature_plies=None, late_temperature=0.0):
+        """root_noise: None or (epsilon, alpha[, seed]), Dirichlet noise on every move's root priors, keyed by the
+        global game id and the ply (Engine.set_root_noise). temperature_plies: moves from that ply on use
+        late_temperature instead of temperature (Engine.set_temperature_schedule). Both off by default."""
+        from .noise import parse_root_noise, parse_temperature_plies
+        self.root_noise = parse_root_noise(root_noise)
+        self.temperature_plies, self.late_temperature = parse_temperature_plies(temperature_plies, late_temperature)
         if lanes < 1 or slots % lanes:
             raise ValueError("slots must be a positive multiple of lanes")
         per = slots // lanes
@@ -442,6 +449,11 @@ class SelfPlay:
                                     lanes > 1))
             if i and cache_log2:  # one table for all lanes: games in different lanes share positions
                 self.lanes[i].engine.share_cache(self.lanes[0].engine)
+        for ln in self.lanes:  # the same settings on every lane's engine: a game's record does not see its lane
+            if self.root_noise is not None:
+                ln.engine.set_root_noise(*self.root_noise)
+            if self.temperature_plies is not None:
+                ln.engine.set_temperature_schedule(self.temperature_plies, self.late_temperature)
         self.engine = self.lanes[0].engine
         self.x = self.lanes[0].x
         self.slots = slots
