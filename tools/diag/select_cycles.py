@@ -6,7 +6,7 @@ aged like the bench, then the phase cycles of the timed moves: per launch, summe
 tree, for all trees and for the heavy trees (>= 24 round trips in the launch, the ones that set a
 launch's length). Each mark drains the wave's memory counters, so the phases do not overlap (the
 instrumented launch is slower than the product's). One JSON line.
-usage: python tools/diag/select_cycles.py [age] [moves] [pretouch 0-3 (engine.hip g_sel_pretouch)]"""
+usage: python tools/diag/select_cycles.py [age] [moves] [pretouch 0-3 (csrc/engine/select.h g_sel_pretouch)]"""
 import ctypes
 import json
 import os

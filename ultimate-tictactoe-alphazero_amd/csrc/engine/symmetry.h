@@ -1,6 +1,6 @@
 // engine/symmetry.h — the round's pending leaves seen through a symmetry of the square, and an evaluator's rows
 // mapped back (uttt_sym.h). A part of engine.hip's one translation unit, like its siblings in
-// engine/. The hashed choice shares the wave's input_words (the hash evaluator's four ballots), which engine.hip
+// engine/. The hashed choice shares the wave's input_words (the hash evaluator's four ballots), which rounds.h
 // defines further down and this header only declares.
 //
 // Both kernels are shaped like k_playout_leaves: one wave per slot, the count read on the device (the grid covers
