@@ -381,6 +381,41 @@ int uttt_search_root_priors(uttt_engine_t *eng, float *priors, int32_t *n_legal)
  * epsilon outside [0, 1] or alpha outside [1/32, 32] (alpha is checked even when epsilon is 0). */
 int uttt_engine_set_root_noise(uttt_engine_t *eng, float epsilon, float alpha, uint64_t seed);
 
+/* Tree reuse (off by default): with it on, a self-play move begin (blocking, _async, and the move
+ * loops built on them) builds each slot's root by k_reroot in place of k_begin. For a live slot whose game
+ * continues, the root's child c with the action the slot played (ply_action[slot][ply - 1]) becomes the new root
+ * and the subtree under it is kept: c's link.k duplicate child sets are merged move by move into one block (N and
+ * link.k summed, W summed in f32 in copy order, P of the first copy: the evaluator's priors, where a fresh root has
+ * 1 / |legal|; the copies' child blocks concatenated in copy order), everything below is copied with re-based
+ * first-child indices, and the pool is laid out breadth first (root, its block, then the child blocks of the nodes
+ * in the order the nodes stand). The new root's record: N = N_c - k_c (the sum of its children's visits), W as
+ * c's (nothing reads a root's W), P 0, no action, link (1, 1). The search starts with sims_done = N_c - k_c, so a
+ * move tops the root up to evaluate_count visits instead of adding evaluate_count: root visits still sum to
+ * evaluate_count and the pool's bound 82 + 81 * max_sims holds. A slot that is not live, holds a new game, or
+ * whose c has no children (never expanded, or terminal) gets the fresh root k_begin writes. Root noise, when on,
+ * is mixed into the carried priors. The trees are copied into a second node pool as large as the first,
+ * allocated when reuse is first switched on and counted by uttt_engine_device_bytes; the two change places every
+ * move. While it is on, uttt_search_begin_mode(UTTT_SEMANTICS_PY) and uttt_search1_begin return UTTT_ERR_ARG (a py
+ * tree's expansions replace; the resident one-tree search keeps its tree in its own wave). It may be called at
+ * any time and holds from the next move begin on. */
+int uttt_engine_set_tree_reuse(uttt_engine_t *eng, int32_t on);
+/* Re-root every tree of a finished uttt_search_begin search (C++ semantics, every leaf applied) at actions[t],
+ * as above, and begin the next search on the carried trees: each runs until its root has evaluate_count visits
+ * (at least the finished search's evaluate_count; the batch size stays). Then select / apply rounds as after
+ * uttt_search_begin. UTTT_ERR_ARG for an action that is -1 or not a legal move of its tree's root (nothing is
+ * changed then), and after a search with Python semantics; UTTT_ERR_ORDER while tree reuse is off. */
+int uttt_search_reroot(uttt_engine_t *eng, const int32_t *actions, int32_t evaluate_count);
+/* One tree's node records, four uint32 each (W f32 bits, P f32 bits, meta = N : 16 | action : 7 | L : 7 | 2 flags,
+ * link = first child : 20 | k : 12; the root is record 0): *node_count records are copied to `records` (room for
+ * `cap` records; NULL: only the count). For tests and analysis; synchronises the stream. */
+int uttt_search_tree(uttt_engine_t *eng, int32_t tree, uint32_t *records, int32_t cap, int32_t *node_count);
+/* What uttt_search_reroot / a reusing move begin makes of one tree, in plain C++ (csrc/uttt_reroot.h): records
+ * (node_count of them, as uttt_search_tree gives them) of a tree whose root's position is *state, re-rooted at
+ * `action`, to out (room for max(node_count, 82) records) and *out_count, bit for bit what the device writes.
+ * UTTT_ERR_ARG for an action that is not a move of the root. Pure CPU. */
+int uttt_reroot_host(const uint32_t *records, int32_t node_count, const uttt_state_t *state, int32_t action,
+                     uint32_t *out, int32_t *out_count);
+
 /* -------------------------------------------------------------- self-play --- */
 /* Self-play of games [game_begin, game_end) (self_play_cpp.py:34-130), each
  * game g with its own numpy-legacy MT19937 seeded seed_base + g (=
@@ -390,7 +425,8 @@ int uttt_engine_set_root_noise(uttt_engine_t *eng, float epsilon, float alpha, u
 int uttt_selfplay_begin(uttt_engine_t *eng, int64_t game_begin, int64_t game_end, uint32_t seed_base,
                         float temperature, int32_t evaluate_count, int32_t batch_size, int64_t arena_plies);
 /* Start one move for every live game: its search tree is rebuilt from the
- * current position (no tree reuse, uttt_mcts.cpp:92). *n_live = live slots
+ * current position (uttt_mcts.cpp:92 has no tree reuse; uttt_engine_set_tree_reuse
+ * carries the played move's subtree over instead). *n_live = live slots
  * (0 = every game finished). Then run select/eval/apply rounds. */
 int uttt_selfplay_move_begin(uttt_engine_t *eng, int32_t *n_live);
 /* Finish the move (self_play_cpp.py:63-92): scores -> f64 policy target
@@ -455,7 +491,7 @@ int uttt_engine_cache_stats2(uttt_engine_t *eng, int64_t *hits, int64_t *misses,
 /* Per-kernel timing with HIP events on the engine's stream (off by default). */
 int uttt_engine_set_timing(uttt_engine_t *eng, int32_t enabled);
 /* kernel: 0 select, 1 apply, 2 encode, 3 scan, 4 move_end, 5 hash_eval, 15 playout, 16 solve,
- * 17 solve_leaves, 18 sym_leaves, 19 sym_rows, 20 root_noise.
+ * 17 solve_leaves, 18 sym_leaves, 19 sym_rows, 20 root_noise, 21 reroot.
  * Outputs total ms, launches and algorithmic bytes. Counters without launches
  * (value in *algo_bytes): 6 tree levels walked by select (sum over descents of depth + 1),
  * 7 trees that descended, 9 sum over select launches of the slowest tree's levels. */

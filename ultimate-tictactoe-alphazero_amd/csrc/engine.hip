@@ -36,6 +36,7 @@
 //   search1.h     Search1Host, k_search1: a one-tree search as one resident wave
 //   selfplay.h    Slot / GameEntry / SelfPlay, k_move_end, k_finalize, MT19937 seeding, k_archive, k_hwc
 //   noise.h       k_root_noise, k_root_priors: Dirichlet noise mixed into the roots' priors, the priors read back
+//   reroot.h      k_reroot: tree reuse, the played move's subtree copied to the front of the tree's other pool
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,8 @@ namespace uttt {
 static_assert(offsetof(Slot, ply) == offsetof(Slot, game) + offsetof(NoiseKey, ply) && offsetof(NoiseKey, stream) == 0,
               "k_root_noise reads a slot's game and ply as one NoiseKey");
 }  // namespace uttt
+// Tree reuse (k_reroot): behind the noise kernels, for the same reason
+#include "engine/reroot.h"
 
 // ============================================================== host side ==
 using namespace uttt;
@@ -115,6 +118,13 @@ struct uttt_engine {
     // what the kernels take by value: raw pointers, filled from the owners below (alloc_n)
     Pool pool{};
     Trees tr{};
+    // tree reuse (uttt_engine_set_tree_reuse): the to-space k_reroot copies into, allocated when reuse is first
+    // switched on; pool.rec and pool2.rec change places after every k_reroot launch
+    Pool pool2{};
+    DevBuf<uint4> m_rec2;
+    DevBuf<int32_t> d_actions;  // uttt_search_reroot's actions
+    bool tree_reuse = false;
+    bool reuse_ready = false;   // pool holds the trees of this self-play run's last ended move
     DevBuf<uint4> m_rec, m_path_rec;
     DevBuf<TreeCtl> m_ctl;
     DevBuf<uttt_state_t> m_root, m_leaf;
@@ -480,6 +490,7 @@ static int search_begin_common(uttt_engine *e, int32_t n_trees, int32_t sims, in
     if (int rc0 = search1_stop(e)) return rc0;  // a resident one-tree search left unfinished
     e->dev_apply_staged = false;  // a staged round of a search that was never ended is dropped with it
     e->host_apply_rows = 0;       // (and a staged one-tree evaluation)
+    e->reuse_ready = false;       // (and the trees a self-play move would have carried over)
     if (n_trees <= 0 || n_trees > e->max_trees) {
         set_error("n_trees %d out of range 1..%d", n_trees, e->max_trees);
         return UTTT_ERR_ARG;
@@ -532,6 +543,13 @@ static int refuse_root_noise(uttt_engine *e, const char *fn, const char *why) {
     return UTTT_ERR_ARG;
 }
 
+// Tree reuse is defined for the C++ semantics' append-only trees built by k_begin / k_reroot only
+static int refuse_tree_reuse(uttt_engine *e, const char *fn, const char *why) {
+    if (!e || !e->tree_reuse) return UTTT_OK;
+    set_error("%s: tree reuse is on (uttt_engine_set_tree_reuse) and %s", fn, why);
+    return UTTT_ERR_ARG;
+}
+
 int uttt_search_begin(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch) {
     return uttt_search_begin_mode(e, roots, n_trees, sims, batch, UTTT_SEMANTICS_CPP);
 }
@@ -541,6 +559,9 @@ int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t 
     if (semantics == UTTT_SEMANTICS_PY)
         if (int rc = refuse_root_noise(e, "uttt_search_begin_mode",
                                        "a py root takes its priors from its first flush: use UTTT_SEMANTICS_CPP"))
+            return rc;
+    if (semantics == UTTT_SEMANTICS_PY)
+        if (int rc = refuse_tree_reuse(e, "uttt_search_begin_mode", "a py tree's expansions replace: use UTTT_SEMANTICS_CPP"))
             return rc;
     if (int rc = begin_with_semantics(e, "uttt_search_begin_mode", roots, n_trees, sims, batch, semantics)) return rc;
     HIP_TRY(hipMemcpyAsync(e->tr.leaf, roots, sizeof(uttt_state_t) * n_trees, hipMemcpyHostToDevice, e->stream));
@@ -737,6 +758,9 @@ int uttt_search1_begin(uttt_engine_t *e, const uttt_state_t *root, int32_t sims,
                        float temperature) {
     if (int rc = refuse_root_noise(e, "uttt_search1_begin",
                                    "the resident one-tree search builds its root itself: use uttt_search_begin"))
+        return rc;
+    if (int rc = refuse_tree_reuse(e, "uttt_search1_begin",
+                                   "the resident one-tree search keeps its tree in its own wave: use uttt_search_begin"))
         return rc;
     // (search_begin_common: a resident wave left by an unfinished search exits first)
     if (int rc = begin_with_semantics(e, "uttt_search1_begin", root, 1, sims, batch, semantics)) return rc;
@@ -1377,6 +1401,99 @@ int uttt_engine_set_root_noise(uttt_engine_t *e, float epsilon, float alpha, uin
     return UTTT_OK;
 }
 
+// ------------------------------------------------------------- tree reuse --
+// k_reroot in place of k_begin: the failure flag zeroed on the stream first (a wave of k_reroot may raise it, so the
+// kernel cannot reset it itself as k_begin does), the launch, and the two pools changing places
+static int launch_reroot(uttt_engine *e, int n, const RerootSrc &src, unsigned long long *err) {
+    HIP_TRY(hipMemsetAsync(e->tr.count + 3, 0, sizeof(int32_t), e->stream));
+    timed_launch(e, kKReroot, k_reroot, dim3(grid_waves(n)), dim3(kBlock), e->pool, e->pool2, e->tr, src, err);
+    std::swap(e->pool.rec, e->pool2.rec);
+    return UTTT_OK;
+}
+
+int uttt_engine_set_tree_reuse(uttt_engine_t *e, int32_t on) {
+    if (!e) return UTTT_ERR_ARG;
+    // (any time: the setting is read when a move begins, and the pool then holds the last ended move's trees
+    // whichever kernel built their roots)
+    HIP_TRY(hipSetDevice(e->device));
+    if (on && !e->m_rec2) {  // the to-space: as large as the node pool, kept once it is there
+        if (int rc = alloc_n(e, e->m_rec2, (size_t)e->max_trees * (size_t)e->cap, &e->pool2.rec)) return rc;
+        e->pool2.cap = e->cap;
+    }
+    e->tree_reuse = on != 0;
+    return UTTT_OK;
+}
+
+int uttt_search_reroot(uttt_engine_t *e, const int32_t *actions, int32_t evaluate_count) {
+    if (!e || !actions) return UTTT_ERR_ARG;
+    if (!e->tree_reuse) {
+        set_error("uttt_search_reroot: tree reuse is off (uttt_engine_set_tree_reuse)");
+        return UTTT_ERR_ORDER;
+    }
+    if (e->selfplay || e->tr.n_trees <= 0 || e->phase != 1) {
+        set_error("uttt_search_reroot: needs a search begun by uttt_search_begin whose leaves are all applied");
+        return UTTT_ERR_ORDER;
+    }
+    if (e->tr.py) {
+        set_error("uttt_search_reroot: the search has Python semantics (its expansions replace): C++ semantics only");
+        return UTTT_ERR_ARG;
+    }
+    if (evaluate_count < e->tr.sims || evaluate_count > e->max_sims) {
+        set_error("uttt_search_reroot: evaluate_count %d out of range %d (the finished search's) .. %d (engine max_sims)",
+                  evaluate_count, e->tr.sims, e->max_sims);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = search1_stop(e)) return rc;
+    if (int rc = flush_host_apply(e)) return rc;
+    if (int rc = check_tree_errors(e)) return rc;
+    const int n = e->tr.n_trees;
+    std::vector<uttt_state_t> roots((size_t)n);
+    HIP_TRY(hipMemcpyAsync(roots.data(), e->tr.root, sizeof(uttt_state_t) * n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int t = 0; t < n; ++t) {
+        uint32_t m[3];
+        legal_mask(roots[t], m);
+        if (actions[t] < 0 || actions[t] > 80 || !bit_of(m, actions[t])) {
+            set_error("uttt_search_reroot: action %d is not a legal move of tree %d's root", actions[t], t);
+            return UTTT_ERR_ARG;
+        }
+    }
+    if (int rc = e->d_actions.grow(e->max_trees)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_actions, actions, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+    e->tr.sims = evaluate_count;
+    const RerootSrc src{nullptr, nullptr, nullptr, e->d_actions.get(), 0};
+    if (int rc = launch_reroot(e, n, src, nullptr)) return rc;
+    launch_root_noise(e, nullptr, 0);
+    if (int rc = check_launch()) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // the caller's actions were read
+    e->phase = 1;
+    e->n_pending = 0;
+    return UTTT_OK;
+}
+
+int uttt_search_tree(uttt_engine_t *e, int32_t tree, uint32_t *records, int32_t cap, int32_t *node_count) {
+    if (!e || !node_count || tree < 0 || tree >= e->tr.n_trees || (records && cap < 0)) {
+        set_error("uttt_search_tree: bad arguments (tree %d of %d)", tree, e ? e->tr.n_trees : 0);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = flush_host_apply(e)) return rc;
+    TreeCtl ctl;
+    HIP_TRY(hipMemcpyAsync(&ctl, e->tr.ctl + tree, sizeof(ctl), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *node_count = ctl.node_count;
+    if (!records) return UTTT_OK;
+    if (ctl.node_count < 0 || ctl.node_count > e->cap || cap < ctl.node_count) {
+        set_error("uttt_search_tree: the tree has %d records, room for %d", ctl.node_count, cap);
+        return UTTT_ERR_ARG;
+    }
+    HIP_TRY(hipMemcpyAsync(records, e->pool.rec + (size_t)tree * e->pool.cap, sizeof(uint4) * (size_t)ctl.node_count,
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return UTTT_OK;
+}
+
 // ----------------------------------------------------------- self-play API --
 int uttt_selfplay_set_temperature_schedule(uttt_engine_t *e, int32_t plies, float late_temperature) {
     if (!e) return UTTT_ERR_ARG;
@@ -1406,6 +1523,7 @@ int uttt_selfplay_begin(uttt_engine_t *e, int64_t game_begin, int64_t game_end, 
     e->tr.py = 0;  // self-play is the cpp/uttt_mcts.cpp path
     if (rc) return rc;
     e->phase = 0;  // move_begin first
+    e->reuse_ready = false;  // no move of this run has ended: the first k_reroot builds every root fresh
     SelfPlay &sp = e->sp;
     if (!e->m_work) {  // the last of the per-slot blocks: all of them are there, or the run cannot start
         if ((rc = alloc_n(e, e->m_slot, slots, &sp.slot)) || (rc = alloc_n(e, e->m_mt_key, (size_t)slots * 624, &sp.mt_key)) ||
@@ -1461,8 +1579,14 @@ static int launch_move_begin(uttt_engine *e) {
     e->host_apply_rows = 0;       // (a one-tree evaluation staged by a search on this engine, never applied)
     e->tr.n_trees = slots;
     e->moves++;
-    hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
-                       (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err.get());
+    if (e->tree_reuse) {  // the played moves' subtrees into the other pool, which becomes the trees' pool
+        const RerootSrc src{e->sp.slot, e->sp.live, e->sp.ply_action, nullptr, e->reuse_ready ? 0 : 1};
+        if (int rc = launch_reroot(e, slots, src, e->d_err.get())) return rc;
+    } else {
+        hipLaunchKernelGGL(k_begin, dim3(grid_waves(slots)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
+                           (const char *)e->sp.slot, (int)sizeof(Slot), (const int32_t *)e->sp.live, e->d_err.get());
+    }
+    e->reuse_ready = false;  // until this move is ended
     launch_root_noise(e, (const char *)e->sp.slot + offsetof(Slot, game), (int)sizeof(Slot));
     if (int rc = check_launch()) return rc;
     e->phase = 1;
@@ -1483,6 +1607,7 @@ static int launch_move_end(uttt_engine *e, const int32_t *fail, const TreeCtl *c
         hipLaunchKernelGGL(k_archive, dim3(archive_grid(slots)), dim3(256), 0, e->stream, e->sp,
                            (const unsigned long long *)err, 1);
     }
+    e->reuse_ready = true;  // the pool now holds the trees the next move's k_reroot reads
     return check_launch();
 }
 

@@ -70,9 +70,10 @@ enum KernelId {
     kKSymLeaves,    // k_sym_leaves launches
     kKSymRows,      // k_sym_rows launches
     kKRootNoise,    // k_root_noise launches
+    kKReroot,       // k_reroot launches
     kKernelCount
 };
-static_assert(kKSolveLeaves == 17 && kKSymRows == 19 && kKRootNoise == 20, "the public header and _lib.KERNELS state the ids");
+static_assert(kKSolveLeaves == 17 && kKSymRows == 19 && kKRootNoise == 20 && kKReroot == 21, "the public header and _lib.KERNELS state the ids");
 
 // Device counters are striped: counter i of a row lives in kStripes 128-byte slots, and a workgroup
 // adds into slot (blockIdx & (kStripes - 1)), so thousands of waves finishing together do not

@@ -10,6 +10,7 @@
 #include "uttt_bits.h"
 #include "uttt_engine.h"
 #include "uttt_noise.h"
+#include "uttt_reroot.h"
 #include "uttt_playout.h"
 #include "uttt_solve.h"
 #include "uttt_sym.h"
@@ -441,6 +442,26 @@ int uttt_root_noise_host(const uttt_state_t *states, int64_t n, const int64_t *s
             if (priors) priors[r * 81 + i] = noise_mix(epsilon, row[i], up);
         }
     }
+    return UTTT_OK;
+}
+
+int uttt_reroot_host(const uint32_t *records, int32_t node_count, const uttt_state_t *state, int32_t action,
+                     uint32_t *out, int32_t *out_count) {
+    // uttt_reroot.h for one tree; what k_reroot writes into the tree's other pool.
+    if (!records || !state || !out || !out_count || node_count < 1) {
+        set_error("uttt_reroot_host: null pointer or an empty tree");
+        return UTTT_ERR_ARG;
+    }
+    if (state->active < -1 || state->active > 8) {
+        set_error("active_board must be -1..8 (the root has %d)", state->active);
+        return UTTT_ERR_ARG;
+    }
+    const int n = reroot::reroot_tree(records, node_count, *state, action, out);
+    if (n < 0) {
+        set_error("uttt_reroot_host: action %d is not a move of the root, or the records are not a search's tree", action);
+        return UTTT_ERR_ARG;
+    }
+    *out_count = n;
     return UTTT_OK;
 }
 

@@ -41,6 +41,7 @@ from uttt_amd.model import DualNetwork  # noqa: E402
 from uttt_amd.distributed import broadcast_int, init_from_env, self_play_sharded  # noqa: E402
 from uttt_amd.history import write_history_file  # noqa: E402
 from uttt_amd.noise import root_noise_from_env, temperature_plies_from_env  # noqa: E402
+from uttt_amd.reuse import tree_reuse_from_env  # noqa: E402
 from uttt_amd.selfplay import SelfPlay, default_lanes, history_from_records, symmetry_from_env  # noqa: E402
 
 SP_GAME_COUNT = 500
@@ -61,9 +62,10 @@ def _fingerprint(model):
 def _exploration():
     """SelfPlay's exploration arguments from the environment (unset: off): UTTT_ROOT_NOISE = "eps,alpha[,seed]",
     Dirichlet noise on every move's root priors; UTTT_TEMPERATURE_PLIES = "n[,late]", moves from ply n on at
-    temperature late (default 0)."""
+    temperature late (default 0); UTTT_TREE_REUSE = 1, every move's search starts from the played move's subtree."""
     plies, late = temperature_plies_from_env()
-    return dict(root_noise=root_noise_from_env(), temperature_plies=plies, late_temperature=late)
+    return dict(root_noise=root_noise_from_env(), temperature_plies=plies, late_temperature=late,
+                tree_reuse=tree_reuse_from_env())
 
 
 def _runner(model, slots):

@@ -18,7 +18,7 @@ ERRORS = {-1: "UTTT_ERR_ARG", -2: "UTTT_ERR_HIP", -3: "UTTT_ERR_CAPACITY", -4: "
           -5: "UTTT_ERR_NODEVICE", -6: "UTTT_ERR_NONFINITE"}
 
 KERNELS = {"select": 0, "apply": 1, "encode": 2, "scan": 3, "move_end": 4, "hash_eval": 5, "playout": 15, "solve": 16,
-           "solve_leaves": 17, "sym_leaves": 18, "sym_rows": 19, "root_noise": 20,
+           "solve_leaves": 17, "sym_leaves": 18, "sym_rows": 19, "root_noise": 20, "reroot": 21,
            # select latency counters (their value is in "bytes"; no launches)
            "select_levels": 6, "select_trees": 7, "select_max_levels_sum": 9,
            "select_trips": 10, "select_max_trips_sum": 12}
@@ -109,6 +109,10 @@ SIGNATURES = {
     "uttt_search_scores": (ctypes.c_int, [_P, _F32, _F32P, _I32P]),
     "uttt_search_root_priors": (ctypes.c_int, [_P, _F32P, _I32P]),
     "uttt_engine_set_root_noise": (ctypes.c_int, [_P, _F32, _F32, _U64]),
+    "uttt_engine_set_tree_reuse": (ctypes.c_int, [_P, _I32]),
+    "uttt_search_reroot": (ctypes.c_int, [_P, _I32P, _I32]),
+    "uttt_search_tree": (ctypes.c_int, [_P, _I32, _U32P, _I32, _I32P]),
+    "uttt_reroot_host": (ctypes.c_int, [_U32P, _I32, _SP, _I32, _U32P, _I32P]),
     "uttt_selfplay_set_temperature_schedule": (ctypes.c_int, [_P, _I32, _F32]),
     "uttt_selfplay_begin": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_uint32, _F32, _I32, _I32, _I64]),
     "uttt_selfplay_move_begin": (ctypes.c_int, [_P, _I32P]),

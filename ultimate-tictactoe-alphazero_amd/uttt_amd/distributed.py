@@ -148,7 +148,7 @@ def broadcast_int(value, src=0):
 
 def self_play_sharded(model, n_games, slots, seed_base, evaluate_count=50, batch_size=8, temperature=1.0,
                       lanes=None, progress=None, evaluator_kind=None, timings=None, symmetry=None, root_noise=None,
-                      temperature_plies=None, late_temperature=0.0):
+                      temperature_plies=None, late_temperature=0.0, tree_reuse=False):
     """Run this rank's contiguous shard of game ids [0, n_games) and gather every rank's records to
     rank 0 (records with inputs on rank 0, None elsewhere). Game g plays from RandomState(seed_base + g)
     whatever the world size, so the gathered records equal a single-GPU run; root_noise and the
@@ -168,7 +168,7 @@ def self_play_sharded(model, n_games, slots, seed_base, evaluate_count=50, batch
         dev = torch.cuda.current_device() if torch.cuda.is_available() else None
         sp = SelfPlay(n_slots, evaluate_count, batch_size, temperature, device=dev, model=model, lanes=n_lanes,
                       evaluator_kind=evaluator_kind, symmetry=symmetry, root_noise=root_noise,
-                      temperature_plies=temperature_plies, late_temperature=late_temperature)
+                      temperature_plies=temperature_plies, late_temperature=late_temperature, tree_reuse=tree_reuse)
         t = sp.run(b, e, seed_base, progress)
         if timings is not None:
             timings["games_s"] = t

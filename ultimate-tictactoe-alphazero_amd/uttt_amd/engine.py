@@ -359,6 +359,31 @@ class Engine:
         check(self.lib.uttt_engine_set_root_noise(self.h, float(epsilon), float(alpha),
                                                   ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
 
+    def set_tree_reuse(self, on=True):
+        """Tree reuse (uttt_engine_set_tree_reuse): self-play moves carry the played move's subtree
+        into the next search, which tops the root up to evaluate_count visits. Off by default. The first call
+        with on=True allocates a second node pool (device_bytes() counts it)."""
+        check(self.lib.uttt_engine_set_tree_reuse(self.h, int(bool(on))))
+
+    def reroot(self, actions, evaluate_count):
+        """Re-root every tree of a finished "cpp" search at actions[t] and begin the next search on the carried
+        trees (uttt_search_reroot): select / apply rounds follow as after search_begin. Needs set_tree_reuse(True).
+        ValueError for an action that is not a legal move of its tree's root."""
+        a = np.ascontiguousarray(actions, np.int32).reshape(-1)
+        if len(a) != self.n_trees:
+            raise ValueError(f"reroot: {len(a)} actions for {self.n_trees} trees")
+        check(self.lib.uttt_search_reroot(self.h, ptr(a, ctypes.c_int32), int(evaluate_count)))
+
+    def tree(self, t):
+        """Tree t's node records as a structured array (reuse.TREE_DTYPE: W, P, N, action, L, first, k), the root
+        at index 0 (uttt_search_tree)."""
+        from . import reuse
+        n = ctypes.c_int32()
+        check(self.lib.uttt_search_tree(self.h, int(t), None, 0, ctypes.byref(n)))
+        raw = np.zeros((max(n.value, 0), 4), np.uint32)
+        check(self.lib.uttt_search_tree(self.h, int(t), ptr(raw, ctypes.c_uint32), len(raw), ctypes.byref(n)))
+        return reuse.unpack(raw[:n.value])
+
     def set_temperature_schedule(self, plies=None, late_temperature=0.0):
         """Self-play moves at ply >= plies use late_temperature instead of selfplay_begin's temperature
         (uttt_selfplay_set_temperature_schedule; between moves, before or after selfplay_begin). plies None:

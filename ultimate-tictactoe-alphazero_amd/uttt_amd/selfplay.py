@@ -431,10 +431,13 @@ class SelfPlay:
 
     def __init__(self, slots, evaluate_count=50, batch_size=8, temperature=1.0, device=None, evaluator=None,
                  model=None, cache_log2=None, cache_clear_every=0, lanes=1, evaluator_kind=None, symmetry=None,
-                 root_noise=None, temperature_plies=None, late_temperature=0.0):
+                 root_noise=None, temperature_plies=None, late_temperature=0.0, tree_reuse=False):
         """root_noise: None or (epsilon, alpha[, seed]), Dirichlet noise on every move's root priors, keyed by the
         global game id and the ply (Engine.set_root_noise). temperature_plies: moves from that ply on use
-        late_temperature instead of temperature (Engine.set_temperature_schedule). Both off by default."""
+        late_temperature instead of temperature (Engine.set_temperature_schedule). tree_reuse: every move's search
+        starts from the subtree under the move just played and tops the root up to evaluate_count visits
+        (Engine.set_tree_reuse). All off by default."""
+        self.tree_reuse = bool(tree_reuse)
         from .noise import parse_root_noise, parse_temperature_plies
         self.root_noise = parse_root_noise(root_noise)
         self.temperature_plies, self.late_temperature = parse_temperature_plies(temperature_plies, late_temperature)
@@ -454,6 +457,8 @@ class SelfPlay:
                 ln.engine.set_root_noise(*self.root_noise)
             if self.temperature_plies is not None:
                 ln.engine.set_temperature_schedule(self.temperature_plies, self.late_temperature)
+            if self.tree_reuse:
+                ln.engine.set_tree_reuse(True)
         self.engine = self.lanes[0].engine
         self.x = self.lanes[0].x
         self.slots = slots
