@@ -70,7 +70,17 @@ int uttt_nn_heads_dev(const float *act, const float *head_weights, const int32_t
  * y_amax row of the conv that produced x), else one bound x_amax[0] for every board (the stem).
  * y_amax (optional): receives max(y) of each board by atomic max (the row must be zero on entry).
  * amax_clear (optional): the kernel zeroes amax_clear[0 .. clear_count), for a later conv's y_amax;
- * it must not be x_amax or y_amax. */
+ * it must not be x_amax or y_amax.
+ * Domain: a board's inputs are finite with 36 * max|x| < 3e38 (max|x| < 8.3e36), the f32 accuracy holds
+ * there (tests/test_conv_edges_gpu.py: up to the transform's growth bound max|V| = 36 max|x|). Outside it
+ * (an Inf, a NaN, a larger maximum) the board's scale is 1, its V overflows f16 and that board's outputs are
+ * NOT its convolution: at least one of them is non-finite (the epilogue's ReLU keeps NaN, as the heads' do),
+ * so the board leaves the tower, and the evaluator, as non-finite rows, which the engine refuses
+ * (UTTT_ERR_NONFINITE). y_amax drops NaN (it receives the maximum of the board's other outputs, +Inf
+ * included); the other boards of the batch are not touched.
+ * uttt_nn_wino3h_weights refuses (UTTT_ERR_ARG) weights with a NaN or an Inf, and weights so small that
+ * u_scale would be no finite float (0 < max|G g G^T| < 2^-113; refused rather than clamped: a clamped
+ * scale would leave U in f16's subnormals). All-zero weights give u_scale 1. */
 int uttt_nn_wino3h_weights(const float *w, uint16_t *u, float *u_scale);
 int uttt_nn_conv3x3_wino3h(const float *x, const uint16_t *u, float u_scale, const float *bias,
                            const float *residual, float *y, const uint32_t *x_amax, int32_t x_amax_per_board,

@@ -94,6 +94,10 @@ __global__ __launch_bounds__(256) void k_stem(const uttt_state_t *__restrict__ l
 // workgroup and shared by its HB boards: with HB = 1 every board streamed them from L2 in
 // chains of dependent loads (84 us for 1,380 boards in the bench, round 3). Each board's
 // arithmetic - order of every sum included - is the same for any HB.
+// The heads' ReLUs keep NaN (fmaxf(v, 0) returns 0 for one), as the tower conv's do (wino3h_impl.h): a
+// non-finite final activation reaches the policy and value rows, where the engine refuses it. Same bits as
+// fmaxf(v, 0.0f) for every other v.
+__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.0f) ? v : 0.0f; }
 constexpr int HB = 8;
 constexpr int HT = 1024;  // threads: 1x1 convs in 64 groups of 16 lanes, FC1 as 4 board groups x 256 units
 __global__ __launch_bounds__(HT) void k_heads(const float *__restrict__ act, const float *__restrict__ hw, int n,
@@ -144,9 +148,9 @@ __global__ __launch_bounds__(HT) void k_heads(const float *__restrict__ act, con
             }
             if (g == 0) {
                 const int bi = i / 81, pos = i % 81;
-                s_h[bi][pos] = fmaxf(a0 + c0, 0.0f);
-                s_h[bi][81 + pos] = fmaxf(a1 + c1, 0.0f);
-                s_h[bi][162 + pos] = fmaxf(a2 + c2, 0.0f);
+                s_h[bi][pos] = relu_keep_nan(a0 + c0);
+                s_h[bi][81 + pos] = relu_keep_nan(a1 + c1);
+                s_h[bi][162 + pos] = relu_keep_nan(a2 + c2);
             }
         }
     }
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(HT) void k_heads(const float *__restrict__ act, con
         const float w2 = hw[UTTT_HEAD_VFC2_W + u];
 #pragma unroll
         for (int r = 0; r < BQ; ++r) {
-            float v = w2 * fmaxf(acc[r], 0.0f);
+            float v = w2 * relu_keep_nan(acc[r]);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
             if (lane == 0) s_v[q + 4 * r][u >> 6] = v;

@@ -98,7 +98,8 @@ int uttt_nn_wino3h_weights(const float *w, uint16_t *u, float *u_scale) {
                 for (int q = 0; q < 5; ++q) {
                     const double v = tg[p][0] * G[q][0] + tg[p][1] * G[q][1] + tg[p][2] * G[q][2];
                     U[((size_t)(p * 5 + q) * C + ci) * C + co] = v;
-                    umax = fabs(v) > umax ? fabs(v) : umax;
+                    // a NaN sticks (the comparison alone dropped it, and a NaN weight was accepted)
+                    umax = (fabs(v) > umax || v != v) ? fabs(v) : umax;
                 }
         }
     if (!std::isfinite(umax)) {
@@ -110,6 +111,15 @@ int uttt_nn_wino3h_weights(const float *w, uint16_t *u, float *u_scale) {
     if (umax > 0.0) {
         frexp(umax, &e);  // 2^(e-1) <= umax < 2^e
         e = 15 - e;
+    }
+    if (e > 127) {
+        // max |U| < 2^-113: su = 2^e is no finite float (the cast gave +inf, which the conv's u_scale > 0
+        // check accepts and whose 1 / (sv su) = 0 turns every output into relu(bias)). Refused, not clamped:
+        // a clamped su would leave U in f16's subnormals, and sv su would overflow in the kernel instead.
+        delete[] U;
+        set_error("uttt_nn_wino3h_weights: weights too small (max |G g G^T| = %g < 2^-113: no finite float u_scale)",
+                  umax);
+        return UTTT_ERR_ARG;
     }
     const double su = ldexp(1.0, e);
     for (int xi = 0; xi < NP; ++xi)

@@ -547,6 +547,12 @@ __device__ __forceinline__ SetScale set_scale(const uint32_t *__restrict__ x_ama
     return sc;
 }
 
+// ReLU that keeps NaN: fmaxf(v, 0) returns 0 for a NaN, which turned a board outside the conv's domain
+// (an Inf, a NaN, 36 max|x| >= 3e38: its V overflows f16 and the transform's inf - inf is NaN) into finite
+// outputs the heads and the engine's non-finite check never saw. One compare (not <=) and a select; for
+// every other v, -0.0 included, the bits of fmaxf(v, 0.0f) (v_max_f32 returns +0 for (-0, +0)).
+__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.0f) ? v : 0.0f; }
+
 // After a set's last chunk: Y[a][b] = sum_v S[a][v] A^T[b][v], scale, bias, residual, ReLU, one 16-byte
 // store per output position straight from registers, per-board output max; S is zeroed for the next set.
 template <bool RES, int MODE>
@@ -652,7 +658,7 @@ __device__ __forceinline__ void set_epilogue(Acc (&S)[15], int st, const SetScal
                 for (int r = 0; r < 4; ++r) o[r] = __builtin_fmaf(acc[r], inv[rt], bb4[r]);
                 if constexpr (RES) o += rv[ab];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = fmaxf(o[r], 0.0f);
+                for (int r = 0; r < 4; ++r) o[r] = relu_keep_nan(o[r]);
                 out[ab] = o;
                 vmax = fmaxf(vmax, fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3])));
             }
@@ -735,7 +741,7 @@ __device__ __forceinline__ void set_epilogue(Acc (&S)[15], int st, const SetScal
                 v += rv[ab];
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.0f);
+            for (int r = 0; r < 4; ++r) v[r] = relu_keep_nan(v[r]);
             floatx4 *dst = reinterpret_cast<floatx4 *>(y + off[rt] + ((ab / 3) * 9 + ab % 3) * C);
             if constexpr (MODE & 8) {  // diagnostic: no output stores (kept live)
                 asm volatile("" ::"v"(v));
