@@ -36,7 +36,9 @@ extern "C" {
  * uttt_search_select_async with the count read on the device):
  * out[n][81][128] = relu(conv3x3(planes, w) + b) with w[27][128] = folded
  * conv_input weight laid out [in_plane*9 + ky*3 + kx][out_channel]
- * (dual_network.py:89-92; planes of uttt_game.cpp:244-280). Engine stream. */
+ * (dual_network.py:89-92; planes of uttt_game.cpp:244-280). Engine stream.
+ * The stem's ReLU keeps NaN, like the conv's and the heads': a NaN weight or bias reaches every output it
+ * is added to (tests/test_stem_heads_gpu.py). */
 int uttt_nn_stem(uttt_engine_t *eng, const float *w, const float *b, float *out);
 /* The same stem from n packed states (any states, e.g. the uttt_cpp.State objects of a
  * pv_mcts_scores flush), on `stream`. */
@@ -125,7 +127,8 @@ int32_t uttt_nn_tower_ctl_words(int32_t max_boards);
 /* Small batches: the conv's 128 output channels split over 2 workgroups per set (same output bits
  * as the persistent kernel). split: -1 automatic (default: up to 28 boards), 0 or 1 never, 2 always. */
 int uttt_nn_wino3h_set_split(int32_t split);
-/* *amax = max(*amax, max |x[i]|) over count floats, as u32 float bits (zero *amax first). */
+/* *amax = max(*amax, max |x[i]|) over count floats, as u32 float bits (zero *amax first).
+ * A NaN among the x[i] is ignored, as y_amax drops one: the result is the maximum of the others. */
 int uttt_nn_amax(const float *x, int64_t count, uint32_t *amax, void *stream);
 
 #ifdef __cplusplus

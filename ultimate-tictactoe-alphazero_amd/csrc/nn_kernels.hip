@@ -36,6 +36,10 @@ __device__ __forceinline__ uint32_t bit3(uint32_t w0, uint32_t w1, uint32_t w2, 
     const uint32_t w = a < 27 ? w0 : (a < 54 ? w1 : w2);
     return (w >> (a % 27)) & 1u;
 }
+// The stem's and the heads' ReLUs keep NaN (fmaxf(v, 0) returns 0 for one), as the tower conv's do
+// (wino3h_impl.h): a NaN stem weight or bias, or a non-finite final activation, reaches the policy and value
+// rows, where the engine refuses it. Same bits as fmaxf(v, 0.0f) for every other v.
+__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.0f) ? v : 0.0f; }
 __global__ __launch_bounds__(256) void k_stem(const uttt_state_t *__restrict__ leaf, const int32_t *__restrict__ tree_of,
                                               int n, const int32_t *__restrict__ n_dev, const float *__restrict__ w,
                                               const float *__restrict__ b, float *__restrict__ out) {
@@ -80,10 +84,10 @@ __global__ __launch_bounds__(256) void k_stem(const uttt_state_t *__restrict__ l
             acc.z += wv.z;
             acc.w += wv.w;
         }
-        acc.x = fmaxf(acc.x, 0.0f);
-        acc.y = fmaxf(acc.y, 0.0f);
-        acc.z = fmaxf(acc.z, 0.0f);
-        acc.w = fmaxf(acc.w, 0.0f);
+        acc.x = relu_keep_nan(acc.x);
+        acc.y = relu_keep_nan(acc.y);
+        acc.z = relu_keep_nan(acc.z);
+        acc.w = relu_keep_nan(acc.w);
         o[i] = acc;
     }
 }
@@ -94,10 +98,6 @@ __global__ __launch_bounds__(256) void k_stem(const uttt_state_t *__restrict__ l
 // workgroup and shared by its HB boards: with HB = 1 every board streamed them from L2 in
 // chains of dependent loads (84 us for 1,380 boards in the bench, round 3). Each board's
 // arithmetic - order of every sum included - is the same for any HB.
-// The heads' ReLUs keep NaN (fmaxf(v, 0) returns 0 for one), as the tower conv's do (wino3h_impl.h): a
-// non-finite final activation reaches the policy and value rows, where the engine refuses it. Same bits as
-// fmaxf(v, 0.0f) for every other v.
-__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.0f) ? v : 0.0f; }
 constexpr int HB = 8;
 constexpr int HT = 1024;  // threads: 1x1 convs in 64 groups of 16 lanes, FC1 as 4 board groups x 256 units
 __global__ __launch_bounds__(HT) void k_heads(const float *__restrict__ act, const float *__restrict__ hw, int n,
