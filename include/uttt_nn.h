@@ -127,6 +127,10 @@ int32_t uttt_nn_tower_ctl_words(int32_t max_boards);
 /* Small batches: the conv's 128 output channels split over 2 workgroups per set (same output bits
  * as the persistent kernel). split: -1 automatic (default: up to 28 boards), 0 or 1 never, 2 always. */
 int uttt_nn_wino3h_set_split(int32_t split);
+/* The persistent kernel's launches use at most `workgroups` workgroups (0, the default: one per CU times
+ * UTTT_WINO3H_GRID), each looping over sets b, b + workgroups, ...: the same output bits for every value.
+ * For tests, which make a workgroup of a small batch walk several sets with it. */
+int uttt_nn_wino3h_set_grid(int32_t workgroups);
 /* *amax = max(*amax, max |x[i]|) over count floats, as u32 float bits (zero *amax first).
  * A NaN among the x[i] is ignored, as y_amax drops one: the result is the maximum of the others. */
 int uttt_nn_amax(const float *x, int64_t count, uint32_t *amax, void *stream);

@@ -126,7 +126,20 @@ int uttt_diag_wino3h_variant(const float *x, const uint16_t *u, float u_scale, c
             hipLaunchKernelGGL((k_wino3p_conv<false, PF_, ALA_>), grid, dim3(NT), 0, st, x, u, u_scale, bias, nullptr, \
                                y, x_amax, 1, nullptr, nullptr, 0, n_boards);                                         \
     } while (0)
+    // the index tables' A/B (round 7): the product's arithmetic with the indices recomputed per item
+#define UTTT_FORM(F)                                                                                                  \
+    do {                                                                                                              \
+        if (res)                                                                                                      \
+            hipLaunchKernelGGL((k_wino3h_conv<true, 0, 3, F>), grid, dim3(NT), 0, st, x, u, u_scale, bias, res, y, \
+                               x_amax, 1, nullptr, nullptr, 0, n_boards, (const int32_t *)nullptr);                   \
+        else                                                                                                          \
+            hipLaunchKernelGGL((k_wino3h_conv<false, 0, 3, F>), grid, dim3(NT), 0, st, x, u, u_scale, bias,        \
+                               nullptr, y, x_amax, 1, nullptr, nullptr, 0, n_boards, (const int32_t *)nullptr);       \
+    } while (0)
     switch (variant) {
+        case 90: UTTT_FORM(0); break;             // rounds 1-6: indices recomputed per item, branchy input loads
+        case 91: UTTT_FORM(kFormBufferX); break;  // buffer-loaded inputs alone
+        case 92: UTTT_FORM(kFormTables); break;   // the index tables alone (variants 0 and 1: the product, both)
         case 1: UTTT_V(kBufferX, 3); break;
         case 2: UTTT_V(kNoALookahead, 4); break;
         case 3: UTTT_V(kNoALookahead, 5); break;
@@ -166,6 +179,7 @@ int uttt_diag_wino3h_variant(const float *x, const uint16_t *u, float u_scale, c
         default: UTTT_V(0, 3);
     }
 #undef UTTT_V
+#undef UTTT_FORM
 #undef UTTT_P
 #undef UTTT_Q
     return hipGetLastError() == hipSuccess ? UTTT_OK : UTTT_ERR_HIP;

@@ -37,7 +37,9 @@
 // four results are four consecutive output channels of one tile) with the previous
 // point's fold (S[a][v] += A^T[a][u] M) spread over the next point's MFMAs (points
 // u = 0 and 4 accumulate into S on the MFMA itself); the
-// next chunk's inputs are in flight meanwhile. Y = S A after a set's last chunk,
+// next chunk's inputs are in flight meanwhile (branch-free buffer loads; where an item is
+// staged and where a transform item reads and writes comes from per-thread tables the
+// workgroup builds once in LDS: wino3h_impl.h, round 7). Y = S A after a set's last chunk,
 // then scale, bias, residual, ReLU, and one 16-byte store per output position
 // straight from registers, output max.
 #include <hip/hip_runtime.h>
@@ -298,6 +300,15 @@ int uttt_nn_wino3h_set_split(int32_t split) {
         return UTTT_ERR_ARG;
     }
     wino3h::g_split = split;
+    return UTTT_OK;
+}
+
+int uttt_nn_wino3h_set_grid(int32_t workgroups) {
+    if (workgroups < 0) {
+        set_error("uttt_nn_wino3h_set_grid: workgroups must be 0 (one per CU x UTTT_WINO3H_GRID) or a positive cap");
+        return UTTT_ERR_ARG;
+    }
+    wino3h::g_grid = workgroups;
     return UTTT_OK;
 }
 

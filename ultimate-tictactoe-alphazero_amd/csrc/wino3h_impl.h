@@ -57,6 +57,7 @@ __host__ __device__ constexpr int at(int a, int u) {
 // Variant bits (diagnostic builds; the product is MODE 0)
 constexpr int kNoALookahead = 1 << 21;  // V fragments read at their own point (frees 16 VGPRs for U prefetch)
 constexpr int kBufferX = 1 << 22;       // input loads as buffer loads, zero beyond the batch: no branches
+                                        // (the product's form since round 7, kFormBufferX: a no-op there)
 constexpr int kFoldBuiltin = 1 << 23;   // fold as compiler-visible ops (hazards padded by the compiler)
 constexpr int kFoldScalar = 1 << 24;    // ... as scalar v_add_f32 / v_fma_f32 pairs (TU built with -fno-slp-vectorize)
 constexpr int kALook2 = 1 << 25;        // V fragments two points ahead (LDS latency) instead of one
@@ -341,12 +342,13 @@ __device__ __forceinline__ void xi_loop(Acc (&S)[15], const char *__restrict__ s
 }
 
 // inputs of chunk `chunk` of the set starting at board b0 -> registers
-template <int MODE>
+// BUF: the branch-free buffer-load form (the product since round 7; kBufferX and kHandoff select it too)
+template <int MODE, bool BUF = false>
 __device__ __forceinline__ void load_x(float4 (&xr)[XPT], const float *__restrict__ x, int b0, int n_boards, int chunk,
                                        int tid) {
     // the staged boards are consecutive: their positions are one run of rows of x
     const int rows = (n_boards - b0) * 81;
-    if constexpr (MODE & (kBufferX | kHandoff)) {
+    if constexpr (BUF || (MODE & (kBufferX | kHandoff))) {
         // one resource per set whose range ends at the batch's last board: loads past it return 0,
         // so no lane branches and the compiler counts the loads exactly (precise vmcnt waits)
         const int nb = min(rows, SB * 81);
@@ -391,7 +393,77 @@ struct SetScale {
     }
 };
 
-// registers -> sX[padded position][32 channels], scaled by its board's sv (a power of two: exact)
+// Index tables (round 7). Where a staging item i = tid + k NT lands in sX, and where transform item `it`
+// reads sX and writes sV, depends on neither the set, the chunk nor the data, yet was recomputed per item in
+// every chunk of every set (divisions by 8, 81, 9 and 3 as mul-hi sequences; hoisted into registers it spilled,
+// hence fresh()). A persistent workgroup now computes each once, in its prologue, into LDS it does not
+// otherwise use, and reads it back where the arithmetic stood: one ds_read per item. Thread t writes and reads
+// only entries t + k NT of s_stage and entry t of s_xform, so the tables need no barrier of their own.
+//   s_stage[i] (u16): bits 0-11 the item's sX offset in 16-byte units (sp * 8 + q), bits 12-13 its staged board
+//     kb, bit 14 set iff i < XF4 (an item past the staged cells stores nothing: its entry is 0).
+//   s_xform[it] (u32): bits 0-8 the staged position of the item's 5x5 window in a set that is half 0 of its
+//     group, bits 9-17 the same for half 1 (whose slot 31 repeats tile 62, as transform_rows' min does),
+//     bits 18-27 the item's sV write base in 4-byte units.
+constexpr int kStageValid = 1 << 14;
+constexpr int NSTAGE = XPT * NT;  // 3,072 entries, 6 KB
+static_assert(XP * (KC / 4) <= (1 << 12) && SB <= 4, "s_stage: 12 bits of offset, 2 of board");
+static_assert((XPT - 1) * NT <= XF4, "only a thread's last staging item can lie past the staged cells");
+static_assert(XP <= (1 << 9) && 4 * VPLANE <= (1 << 12), "s_xform: 9 bits per position, 10 of write base");
+constexpr int kTableBytes = NSTAGE * 2 + NT * 4;
+static_assert(XP * KC * 4 + VB + SB * 4 + 2 * 4 + kTableBytes <= 160 * 1024, "LDS with the index tables (and s_bmax, s_next)");
+
+__host__ __device__ constexpr uint32_t stage_entry(int i) {
+    if (i >= XF4) return 0u;
+    const int q = i % (KC / 4), bp = i / (KC / 4);
+    const int kb = bp / 81, pos = bp - 81 * kb, sp = spos(kb, pos / 9, pos % 9);
+    return (uint32_t)(sp * (KC / 4) + q) | (uint32_t)(kb << 12) | (uint32_t)kStageValid;
+}
+// staged position of the window of transform item `it` in half h of a group (as transform_rows)
+__host__ __device__ constexpr int xform_pos(int it, int h) {
+    const int lt = it / (KC / 2);
+    const int gt = 32 * h + lt < GB * 9 - 1 ? 32 * h + lt : GB * 9 - 1, gb = gt / 9, tt = gt - 9 * gb;
+    return spos(gb - 3 * h, 3 * (tt / 3) - 1, 3 * (tt % 3) - 1);
+}
+// sV write base (bytes) of transform item `it` (as transform_cols)
+__host__ __device__ constexpr int xform_base(int it) {
+    const int p = it % (KC / 2), lt = it / (KC / 2);
+    const int rt = lt >> 4, m = lt & 15, kq = p >> 2, w = p & 3;
+    return rt * 2 * VPLANE + kq * 256 + ((m ^ (2 * kq)) * 16) + 4 * w;
+}
+__host__ __device__ constexpr uint32_t xform_entry(int it) {
+    return (uint32_t)xform_pos(it, 0) | ((uint32_t)xform_pos(it, 1) << 9) | ((uint32_t)(xform_base(it) >> 2) << 18);
+}
+struct IndexTables {
+    uint16_t *stage;  // [NSTAGE]
+    uint32_t *xform;  // [NT]
+};
+// prologue: this thread's entries (NT threads)
+__device__ __forceinline__ void build_tables(const IndexTables &tb, int tid) {
+#pragma unroll
+    for (int k = 0; k < XPT; ++k) tb.stage[tid + k * NT] = (uint16_t)stage_entry(tid + k * NT);
+    tb.xform[tid] = xform_entry(tid);
+}
+
+// registers -> sX[padded position][32 channels], scaled by its board's sv (a power of two: exact):
+// the table form (NT threads; tid may be an opaque copy, the entries are the thread's own)
+__device__ __forceinline__ void store_x(float *__restrict__ sX, const float4 (&xr)[XPT], const SetScale &sc, int tid,
+                                        const IndexTables &tb) {
+#pragma unroll
+    for (int k = 0; k < XPT; ++k) {
+        const uint32_t e = tb.stage[tid + k * NT];
+        if (k + 1 < XPT || (e & kStageValid)) {
+            const float sv = sc.of((int)((e >> 12) & 3u));
+            float4 v = xr[k];
+            v.x *= sv;
+            v.y *= sv;
+            v.z *= sv;
+            v.w *= sv;
+            *reinterpret_cast<float4 *>(reinterpret_cast<char *>(sX) + ((e & 0xfffu) << 4)) = v;
+        }
+    }
+}
+
+// the same by arithmetic (kernels that stage too few chunks to repay a table; diagnostics)
 __device__ __forceinline__ void store_x(float *__restrict__ sX, const float4 (&xr)[XPT], const SetScale &sc, int tid) {
 #pragma unroll
     for (int k = 0; k < XPT; ++k) {
@@ -451,10 +523,8 @@ __device__ __forceinline__ void split(floatx2 v, uint32_t &hi, uint32_t &lo) {
 // group -> split -> sV in fragment order, in two halves: transform_rows (u = d B; reads sX
 // only) and transform_cols (V = B^T u, split, LDS stores into sV). Slot 31 of the second half has no tile: it repeats tile 62, whose
 // results the epilogue drops.
-__device__ __forceinline__ void transform_rows(floatx2 (&uu)[5][5], const float *__restrict__ sX, int it, int h) {
-    const int p = it % (KC / 2), lt = it / (KC / 2);
-    const int gt = min(32 * h + lt, GB * 9 - 1), gb = gt / 9, tt = gt - 9 * gb, ty = tt / 3, tx = tt % 3;
-    const float *xs = sX + spos(gb - 3 * h, 3 * ty - 1, 3 * tx - 1) * KC + 2 * p;
+// xs: the window's first cell, this item's channel pair
+__device__ __forceinline__ void transform_rows(floatx2 (&uu)[5][5], const float *__restrict__ xs) {
     // one row of d live at a time (loads one row ahead; fenced so the scheduler does not
     // hoist all 25 of them next to the fifteen live accumulators)
     floatx2 d[2][5];
@@ -473,11 +543,9 @@ __device__ __forceinline__ void transform_rows(floatx2 (&uu)[5][5], const float 
 }
 
 template <bool MIX = true, bool HI = false>
-__device__ __forceinline__ void transform_cols(char *__restrict__ sv, const floatx2 (&uu)[5][5], int it) {
-    const int p = it % (KC / 2), lt = it / (KC / 2);
-    // A fragment: lane (row m, kq) holds k = 8kq..8kq+7; channel pair p is k = 2p, 2p+1
-    const int rt = lt >> 4, m = lt & 15, kq = p >> 2, w = p & 3;
-    char *base = sv + rt * 2 * VPLANE + kq * 256 + ((m ^ (2 * kq)) * 16) + 4 * w;
+__device__ __forceinline__ void transform_cols(char *__restrict__ base, const floatx2 (&uu)[5][5]) {
+    // base: the item's 4 bytes of its lane's slot. A fragment: lane (row m, kq) holds k = 8kq..8kq+7;
+    // channel pair p is k = 2p, 2p+1 (xform_base)
 #pragma unroll
     for (int b = 0; b < 5; ++b) {
         const floatx2 col[5] = {uu[0][b], uu[1][b], uu[2][b], uu[3][b], uu[4][b]};
@@ -497,8 +565,18 @@ __device__ __forceinline__ void transform_cols(char *__restrict__ sv, const floa
 template <bool MIX = true, bool HI = false>
 __device__ __forceinline__ void transform(char *__restrict__ sv, const float *__restrict__ sX, int it, int h) {
     floatx2 uu[5][5];
-    transform_rows(uu, sX, it, h);
-    transform_cols<MIX, HI>(sv, uu, it);
+    transform_rows(uu, sX + xform_pos(it, h) * KC + 2 * (it % (KC / 2)));
+    transform_cols<MIX, HI>(sv + xform_base(it), uu);
+}
+
+// the table form: item `it` is this thread's own (NT threads); both addresses from the thread's s_xform entry
+template <bool MIX = true, bool HI = false>
+__device__ __forceinline__ void transform(char *__restrict__ sv, const float *__restrict__ sX, int it, int h,
+                                          const IndexTables &tb) {
+    const uint32_t e = tb.xform[it];
+    floatx2 uu[5][5];
+    transform_rows(uu, sX + ((e >> (9 * h)) & 511u) * KC + 2 * (it % (KC / 2)));
+    transform_cols<MIX, HI>(sv + ((e >> 16) & 0xffcu), uu);
 }
 
 // An opaque copy: index math derived from it is recomputed where it is used
@@ -793,7 +871,7 @@ __device__ unsigned int g_stamp[64][2][8][6];
 #endif
 
 // MODE (timing ablations only; 0 in the product): 1 skip the transform, 2 skip the
-// point GEMMs, 64 skip the fold, 512 plain (L2-allocating) input loads, 65536 nontemporal
+// point GEMMs, 64 skip the fold, 512 plain (L2-allocating) input loads (FORM without kFormBufferX), 65536 nontemporal
 // residual loads, 131072 nontemporal output stores.
 // The product streams the conv input with nontemporal loads: 8 lanes read one whole 128-B
 // line, each line once per launch, and L2-allocating them would evict U (1.6 MB, re-read
@@ -802,7 +880,12 @@ __device__ unsigned int g_stamp[64][2][8][6];
 // row, so the two waves that share a 128-B line meet in L2 instead of each moving the line
 // to or from HBM (residual conv 106.7 -> 91.0 us at 1,344 boards, round 2,
 // tools/diag/wino3h_modes.py).
-template <bool RES, int MODE = 0, int PF = 3>
+// FORM (round 7; the product has both, the diagnostics library instantiates the others for the A/B):
+// kFormTables: the staging and transform indices from the workgroup's LDS tables, else recomputed per item as in
+// rounds 1-6; kFormBufferX: the input loads branch-free through a buffer resource (load_x's BUF), else the
+// per-lane bounds branches of rounds 1-6.
+constexpr int kFormTables = 1, kFormBufferX = 2;
+template <bool RES, int MODE = 0, int PF = 3, int FORM = kFormTables | kFormBufferX>
 __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x, const uint16_t *__restrict__ u,
                                                     float u_scale, const float *__restrict__ bias,
                                                     const float *__restrict__ res, float *__restrict__ y,
@@ -812,6 +895,10 @@ __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x,
     // sX [padded position][channel] (border = 0) then sV
     __shared__ __attribute__((aligned(16))) char smem[XP * KC * 4 + VB];
     __shared__ uint32_t s_bmax[SB];
+    constexpr bool TAB = (FORM & kFormTables) != 0, BUF = (FORM & kFormBufferX) != 0;
+    __shared__ uint16_t s_stage[TAB ? NSTAGE : 1];
+    __shared__ uint32_t s_xform[TAB ? NT : 1];
+    const IndexTables tb = {s_stage, s_xform};
     float *const sX = reinterpret_cast<float *>(smem);
     char *const sV = smem + XP * KC * 4;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -869,7 +956,7 @@ __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x,
         zero_pads();
         __syncthreads();
     }
-    load_x<MODE>(xr, x, set_b0(0), n_boards, chunk_of(0), tid);
+    load_x<MODE, BUF>(xr, x, set_b0(0), n_boards, chunk_of(0), tid);
     SetScale sc = set_scale(x_amax, x_amax_per_board, set_b0(0), n_boards);  // V scales of the current set
     // kStagger (diagnostic): waves 4-7 start their point walk at kStaggerRot
     const int rot = ((MODE & kStagger) && wv >= 4) ? kStaggerRot : 0;
@@ -877,7 +964,12 @@ __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x,
 #pragma unroll
     for (int i = 0; i < PF; ++i) bq[i] = load_b<(MODE & kF16) != 0>(ur, (i + rot) % NP, c_rot, voff);
     if constexpr (!(MODE & kSerialPrologue)) zero_pads();
-    store_x(sX, xr, sc, tid);
+    if constexpr (TAB) {
+        build_tables(tb, fresh(tid));  // while the first loads are in flight
+        store_x(sX, xr, sc, fresh(tid), tb);
+    } else {
+        store_x(sX, xr, sc, tid);
+    }
     __syncthreads();
     const bool stamp = (MODE & 4) && blockIdx.x < 64 && (tid == 0 || tid == 256);
     auto mark = [&](int g, int k, unsigned long long t0) {
@@ -902,15 +994,21 @@ __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x,
         // free then; the point loop needs nearly all of them)
         if (!(MODE & kEarlyLoad) || g == 0 || c == 0)
             if (!((MODE & kEpiLoad) && c == 0 && g > 0))  // kEpiLoad: requested before the last epilogue
-                if (g + 1 < G) load_x<MODE>(xr, x, set_b0(g + 1), n_boards, chunk_of(g + 1), fresh(tid));
+                if (g + 1 < G) load_x<MODE, BUF>(xr, x, set_b0(g + 1), n_boards, chunk_of(g + 1), fresh(tid));
         // the next chunk's V scales: this set's, or the next set's after its last chunk
         SetScale sc_next = sc;
         if (c == NCH - 1 && g + 1 < G) sc_next = set_scale(x_amax, x_amax_per_board, set_b0(g + 1), n_boards);
         mark(g, 0, t0);
-        if constexpr ((MODE & 3) != 1) transform<!(MODE & kSplitCvt), (MODE & kF16) != 0>(sV, sX, fresh(tid), set_of(g) & 1);
+        if constexpr ((MODE & 3) != 1) {
+            if constexpr (TAB) transform<!(MODE & kSplitCvt), (MODE & kF16) != 0>(sV, sX, fresh(tid), set_of(g) & 1, tb);
+            else transform<!(MODE & kSplitCvt), (MODE & kF16) != 0>(sV, sX, fresh(tid), set_of(g) & 1);
+        }
         mark(g, 1, t0);
         lds_barrier();
-        if (g + 1 < G) store_x(sX, xr, sc_next, fresh(tid));
+        if (g + 1 < G) {
+            if constexpr (TAB) store_x(sX, xr, sc_next, fresh(tid), tb);
+            else store_x(sX, xr, sc_next, fresh(tid));
+        }
         mark(g, 2, t0);
         if constexpr (MODE & kEpiPrio)
             if (c == NCH - 1 && wv >= 4) __builtin_amdgcn_s_setprio(1);
@@ -928,9 +1026,9 @@ __global__ __launch_bounds__(NT) void k_wino3h_conv(const float *__restrict__ x,
             if (c == NCH - 1) __builtin_amdgcn_s_barrier();
         mark(g, 3, t0);
         if constexpr (MODE & kEarlyLoad)
-            if (c != NCH - 1 && g + 2 < G) load_x<MODE>(xr, x, set_b0(g + 2), n_boards, chunk_of(g + 2), fresh(tid));
+            if (c != NCH - 1 && g + 2 < G) load_x<MODE, BUF>(xr, x, set_b0(g + 2), n_boards, chunk_of(g + 2), fresh(tid));
         if constexpr (MODE & kEpiLoad)
-            if (c == NCH - 1 && g + 2 < G) load_x<MODE>(xr, x, set_b0(g + 2), n_boards, chunk_of(g + 2), fresh(tid));
+            if (c == NCH - 1 && g + 2 < G) load_x<MODE, BUF>(xr, x, set_b0(g + 2), n_boards, chunk_of(g + 2), fresh(tid));
         if (c == NCH - 1)
             set_epilogue<RES, MODE>(S, set_of(g), sc, u_scale, bb4, res, y, y_amax, n_boards, tid, lane, 0, s_bmax);
         sc = sc_next;
@@ -983,7 +1081,7 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 // workgroup of this launch that still reads this block's ticket never sees it reset: the workgroup that
 // finishes the launch's last item (items-done counter, [32]) resets the OTHER block (ticket [0], items
 // [32], done[g] [64 + g]) for the next launch and clears max row 0.
-template <int MODE = kHandoff, int PF = 3>
+template <int MODE = kHandoff, int PF = 3, bool TAB = true>
 __global__ __launch_bounds__(NT) void k_wino3t_tower(float *act, int64_t act_stride, const uint16_t *__restrict__ u_all,
                                                      const float *__restrict__ u_scale_all,
                                                      const float *__restrict__ bias_all, int n_layers,
@@ -994,6 +1092,9 @@ __global__ __launch_bounds__(NT) void k_wino3t_tower(float *act, int64_t act_str
     __shared__ __attribute__((aligned(16))) char smem[XP * KC * 4 + VB];
     __shared__ uint32_t s_bmax[SB];
     __shared__ int s_next[2];  // the next ticket, whether its dependency was seen met
+    __shared__ uint16_t s_stage[TAB ? NSTAGE : 1];
+    __shared__ uint32_t s_xform[TAB ? NT : 1];
+    const IndexTables tb = {s_stage, s_xform};
     float *const sX = reinterpret_cast<float *>(smem);
     char *const sV = smem + XP * KC * 4;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1036,6 +1137,7 @@ __global__ __launch_bounds__(NT) void k_wino3t_tower(float *act, int64_t act_str
     // a ticket, or `total` once they are all taken (a workgroup that finds none takes nothing)
     if (tid == 0) s_next[0] = ld_sc1(ctl) >= (uint32_t)total ? total : (int)atomicAdd(ctl, 1u);
     if (tid < SB) s_bmax[tid] = 0u;
+    if constexpr (TAB) build_tables(tb, fresh(tid));
     for (int i = fresh(tid); i < NPAD * (KC / 4); i += NT) {  // the staged layout's zero pads (never rewritten)
         const int j = i / (KC / 4), q = i % (KC / 4);
         const int pos = j < 50 ? (j / 10) * 10 * SR + j % 10
@@ -1074,7 +1176,8 @@ __global__ __launch_bounds__(NT) void k_wino3t_tower(float *act, int64_t act_str
             load_x<MODE>(xr, in_of(l), b0, n_boards, 0, fresh(tid));
 #pragma unroll
             for (int i = 0; i < PF; ++i) bq[i] = load_b(ur, i, 0, voff);
-            store_x(sX, xr, sc, fresh(tid));
+            if constexpr (TAB) store_x(sX, xr, sc, fresh(tid), tb);
+            else store_x(sX, xr, sc, fresh(tid));
             __syncthreads();
         }
         // conv l+1's max row starts from zero on this set's boards (conv l+1 runs after both sets signal)
@@ -1110,9 +1213,13 @@ __global__ __launch_bounds__(NT) void k_wino3t_tower(float *act, int64_t act_str
                 s_next[0] = t < total ? t : total;
                 s_next[1] = ready;
             }
-            transform<true, false>(sV, sX, fresh(tid), h);
+            if constexpr (TAB) transform<true, false>(sV, sX, fresh(tid), h, tb);
+            else transform<true, false>(sV, sX, fresh(tid), h);
             lds_barrier();
-            if (c + 1 < NCH || nready) store_x(sX, xr, sc_next, fresh(tid));
+            if (c + 1 < NCH || nready) {
+                if constexpr (TAB) store_x(sX, xr, sc_next, fresh(tid), tb);
+                else store_x(sX, xr, sc_next, fresh(tid));
+            }
             {
                 AFrag a0 = load_a(sv_lane, 0), an;
                 floatx2 mprev[4];
@@ -1253,7 +1360,11 @@ static int split_for(int n_boards) {
 // Workgroups per launch: at most cap, cap = CUs x UTTT_WINO3H_GRID (a real number, default 1:
 // persistent, a workgroup loops over sets b, b + grid, ...; 0 = one workgroup per set, so the
 // dispatcher hands sets of concurrent launches to whichever CU frees first)
+// g_grid > 0 (uttt_nn_wino3h_set_grid; tests): at most that many workgroups, so that a small batch walks a
+// workgroup over several sets
+inline int g_grid = 0;
 static int grid_size(int n_boards) {
+    if (g_grid > 0) return n_sets(n_boards) < g_grid ? n_sets(n_boards) : g_grid;
     static int cap = -1;
     if (cap < 0) {
         int dev = 0, cus = 0;

@@ -146,6 +146,7 @@ SIGNATURES = {
     "uttt_nn_tower_ctl_words": (ctypes.c_int32, [_I32]),
     "uttt_nn_amax": (ctypes.c_int, [_P, _I64, _P, _P]),
     "uttt_nn_wino3h_set_split": (ctypes.c_int, [_I32]),
+    "uttt_nn_wino3h_set_grid": (ctypes.c_int, [_I32]),
 }
 
 _lib = None
