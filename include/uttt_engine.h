@@ -416,6 +416,68 @@ int uttt_search_tree(uttt_engine_t *eng, int32_t tree, uint32_t *records, int32_
 int uttt_reroot_host(const uint32_t *records, int32_t node_count, const uttt_state_t *state, int32_t action,
                      uint32_t *out, int32_t *out_count);
 
+/* ------------------------------------------------------------------ match --- */
+/* A match between two players with every game resident on the device (csrc/uttt_match.h): the
+ * loop of evaluate_network.py:78-92 over play() (:33-54), each player an engine of its own. Game g starts at
+ * openings[g / 2] when the match is paired and at openings[g] when not, and player g % 2 takes the side to move
+ * at the start position (:82-85: the players swap from game to game), so games 2 i and 2 i + 1 are one opening
+ * with the colours swapped. Per game the match holds the position, the ply counted from the start position, the
+ * actions played and a result: -1 while the game is live, else player 0's half-points 0 / 1 / 2 (:26-30 times
+ * two, from player 0's side as :83 / :85 count them).
+ *
+ * One iteration of the caller's loop: uttt_match_counts; for each player whose list is not empty
+ * uttt_match_search_begin, the ordinary select / evaluator / apply rounds on that player's engine, and
+ * uttt_match_move; then uttt_match_lists. The match ends when both lists are empty. Both engines run on the
+ * stream given to uttt_match_begin (uttt_engine_set_stream).
+ *
+ * Out of scope, and refused by uttt_match_search_begin with UTTT_ERR_ARG while they are on: root noise (a plain
+ * search keys it by tree index, which here changes from ply to ply) and tree reuse. */
+typedef struct uttt_match uttt_match_t;
+/* Room for max_games games (1 .. 2^20 - 1) on `device` (-1 = the calling thread's current device). */
+int uttt_match_create(int32_t device, int32_t max_games, uttt_match_t **out);
+int uttt_match_destroy(uttt_match_t *m);
+/* The argument check of uttt_match_begin, pure CPU: UTTT_ERR_ARG with a message for a NULL or terminal opening
+ * (:43 would end such a game before its first move), games outside 1..max_games, `paired` with an odd `games`,
+ * and n_openings below what the games need (games / 2 when paired, else games). */
+int uttt_match_check_host(const uttt_state_t *openings, int32_t n_openings, int32_t games, int32_t max_games,
+                          int32_t paired);
+/* Start a match (:33-38's initial state, for every game at once): openings are host states; moves at a ply below
+ * sample_plies are drawn in proportion to the visit counts with `seed`, later ones are the most visited move.
+ * `stream`: a hipStream_t (NULL = the null stream). Builds the first lists; synchronises the stream. */
+int uttt_match_begin(uttt_match_t *m, const uttt_state_t *openings, int32_t n_openings, int32_t games, int32_t paired,
+                     int32_t sample_plies, uint64_t seed, void *stream);
+/* Synchronises the stream and returns out[0..4] = {games in which player 0 is to move, games in which player 1
+ * is, games finished, player 0's half-points over the finished games, finished games that were drawn}
+ * (:79-92's total_point, kept in integers). */
+int uttt_match_counts(uttt_match_t *m, int64_t out[5]);
+/* Begin a plain search of `eng` on the positions of `player`'s list (:47-48: the player to move searches), device
+ * to device: uttt_search_begin_mode's checks and root kernel, with the tree count the list length that
+ * uttt_match_counts last returned; tree t is the t-th game of the list. UTTT_ERR_ORDER if the lists are stale (no
+ * uttt_match_counts since uttt_match_lists, or `player` has moved since); UTTT_ERR_ARG for an empty list, an
+ * engine on another stream or device, and root noise or tree reuse on. Then select / evaluator / apply rounds. */
+int uttt_match_search_begin(uttt_match_t *m, uttt_engine_t *eng, int32_t player, int32_t evaluate_count,
+                            int32_t batch_size, int32_t semantics);
+/* Play the searched move in every game of `player`'s list (:48-51): the search begun by uttt_match_search_begin
+ * on `eng` must have every leaf applied; a failed tree is reported here, as by uttt_search_root_visits. Launches
+ * the root-visit kernel and k_match_move on the engine's stream and returns at once. UTTT_ERR_ORDER without that
+ * search, and for a second move of `player` before uttt_match_lists. */
+int uttt_match_move(uttt_match_t *m, uttt_engine_t *eng, int32_t player);
+/* Rebuild both players' lists and root arrays and the counters (:41-44: finished games leave the loop). Once per
+ * iteration, after both players have moved; returns at once. */
+int uttt_match_lists(uttt_match_t *m);
+/* Host copies of the games' state: results[g] (int8: -1 live, else player 0's half-points), plies[g], actions
+ * [g][81] (int8, -1 past the ply) and states[g]. Any pointer may be NULL. Synchronises the stream. */
+int uttt_match_games(uttt_match_t *m, int8_t *results, int32_t *plies, int8_t *actions, uttt_state_t *states);
+/* The move rule in plain C++ (csrc/uttt_match.h), bit for bit what k_match_move writes (:48-51 for one game):
+ * visits are the root's n_visits counts in legal order (n_visits must be the state's legal count, counts
+ * non-negative); *next, *action and *result (-1, or player 0's half-points) are written. Pure CPU. UTTT_ERR_ARG
+ * for a terminal state, a row of another length, a negative count, or a ply outside 0..80. */
+int uttt_match_move_host(const uttt_state_t *state, const int32_t *visits, int32_t n_visits, int32_t ply,
+                         int64_t game, uint64_t seed, int32_t sample_plies, uttt_state_t *next, int32_t *action,
+                         int32_t *result);
+/* The 64-bit draw of (seed, game, ply) that a sampled move of :48 uses in place of np.random.choice's. Pure CPU. */
+uint64_t uttt_match_draw_host(uint64_t seed, int64_t game, int32_t ply);
+
 /* -------------------------------------------------------------- self-play --- */
 /* Self-play of games [game_begin, game_end) (self_play_cpp.py:34-130), each
  * game g with its own numpy-legacy MT19937 seeded seed_base + g (=

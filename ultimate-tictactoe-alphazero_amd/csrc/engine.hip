@@ -37,6 +37,7 @@
 //   selfplay.h    Slot / GameEntry / SelfPlay, k_move_end, k_finalize, MT19937 seeding, k_archive, k_hwc
 //   noise.h       k_root_noise, k_root_priors: Dirichlet noise mixed into the roots' priors, the priors read back
 //   reroot.h      k_reroot: tree reuse, the played move's subtree copied to the front of the tree's other pool
+//   match.h       Match, k_match_move, k_match_lists: two players' games on the device, the searched move played
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -78,6 +79,8 @@ static_assert(offsetof(Slot, ply) == offsetof(Slot, game) + offsetof(NoiseKey, p
 }  // namespace uttt
 // Tree reuse (k_reroot): behind the noise kernels, for the same reason
 #include "engine/reroot.h"
+// Match play (k_match_move, k_match_lists): the last of all, for the same reason
+#include "engine/match.h"
 
 // ============================================================== host side ==
 using namespace uttt;
@@ -554,22 +557,27 @@ int uttt_search_begin(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_tre
     return uttt_search_begin_mode(e, roots, n_trees, sims, batch, UTTT_SEMANTICS_CPP);
 }
 
-int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch,
-                           int32_t semantics) {
+// A plain search's begin for roots in host memory (uttt_search_begin_mode) or on the device (uttt_match_search_begin;
+// kind says which): the checks, the copy into the trees' leaf slots, k_begin, and the root noise when it is on
+static int search_begin_roots(uttt_engine *e, const char *fn, const uttt_state_t *roots, int32_t n_trees, int32_t sims,
+                              int32_t batch, int32_t semantics, hipMemcpyKind kind) {
     if (semantics == UTTT_SEMANTICS_PY)
-        if (int rc = refuse_root_noise(e, "uttt_search_begin_mode",
-                                       "a py root takes its priors from its first flush: use UTTT_SEMANTICS_CPP"))
+        if (int rc = refuse_root_noise(e, fn, "a py root takes its priors from its first flush: use UTTT_SEMANTICS_CPP"))
             return rc;
     if (semantics == UTTT_SEMANTICS_PY)
-        if (int rc = refuse_tree_reuse(e, "uttt_search_begin_mode", "a py tree's expansions replace: use UTTT_SEMANTICS_CPP"))
-            return rc;
-    if (int rc = begin_with_semantics(e, "uttt_search_begin_mode", roots, n_trees, sims, batch, semantics)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->tr.leaf, roots, sizeof(uttt_state_t) * n_trees, hipMemcpyHostToDevice, e->stream));
+        if (int rc = refuse_tree_reuse(e, fn, "a py tree's expansions replace: use UTTT_SEMANTICS_CPP")) return rc;
+    if (int rc = begin_with_semantics(e, fn, roots, n_trees, sims, batch, semantics)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->tr.leaf, roots, sizeof(uttt_state_t) * n_trees, kind, e->stream));
     hipLaunchKernelGGL(k_begin, dim3(grid_waves(n_trees)), dim3(kBlock), 0, e->stream, e->pool, e->tr,
                        (const char *)e->tr.leaf, (int)sizeof(uttt_state_t), (const int32_t *)nullptr,
                        (unsigned long long *)nullptr);
     launch_root_noise(e, nullptr, 0);
     return check_launch();
+}
+
+int uttt_search_begin_mode(uttt_engine_t *e, const uttt_state_t *roots, int32_t n_trees, int32_t sims, int32_t batch,
+                           int32_t semantics) {
+    return search_begin_roots(e, "uttt_search_begin_mode", roots, n_trees, sims, batch, semantics, hipMemcpyHostToDevice);
 }
 
 static int flush_host_apply(uttt_engine *e);
@@ -1491,6 +1499,215 @@ int uttt_search_tree(uttt_engine_t *e, int32_t tree, uint32_t *records, int32_t 
     HIP_TRY(hipMemcpyAsync(records, e->pool.rec + (size_t)tree * e->pool.cap, sizeof(uint4) * (size_t)ctl.node_count,
                            hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return UTTT_OK;
+}
+
+// ------------------------------------------------------------------ match --
+}  // extern "C"
+
+// A match's memory has the engine's one-owner buffers: `delete m` frees every block
+struct uttt_match {
+    int device = 0;
+    int max_games = 0;
+    hipStream_t stream = nullptr;
+    Match mt{};  // what the kernels take by value: raw pointers, filled from the owners below
+    DevBuf<uttt_state_t> d_state, d_roots;
+    DevBuf<int32_t> d_ply, d_list;
+    DevBuf<int8_t> d_action, d_result;
+    PinBuf<int64_t> h_counts;  // k_match_lists' five counters
+    bool begun = false;
+    bool have_counts = false;        // uttt_match_counts has read the counters of the last k_match_lists
+    bool moved[2] = {false, false};  // the player has moved since the last k_match_lists: its list is stale
+    uttt_engine *searching[2] = {nullptr, nullptr};  // the engine whose search uttt_match_search_begin began
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+};
+
+static int match_player_check(const char *fn, uttt_match *m, uttt_engine *e, int32_t player) {
+    if (!m || !e || (player != 0 && player != 1)) {
+        set_error("%s: null match or engine, or a player other than 0 and 1", fn);
+        return UTTT_ERR_ARG;
+    }
+    if (!m->begun) {
+        set_error("%s: call uttt_match_begin first", fn);
+        return UTTT_ERR_ORDER;
+    }
+    if (e->device != m->device || e->stream != m->stream) {
+        set_error("%s: the engine runs on another device or stream than the match (uttt_engine_set_stream)", fn);
+        return UTTT_ERR_ARG;
+    }
+    return UTTT_OK;
+}
+
+static int launch_match_lists(uttt_match *m) {
+    hipLaunchKernelGGL(k_match_lists, dim3(1), dim3(1024), 0, m->stream, m->mt, m->h_counts.get());
+    m->have_counts = false;
+    m->moved[0] = m->moved[1] = false;
+    m->searching[0] = m->searching[1] = nullptr;
+    return check_launch();
+}
+
+extern "C" {
+
+int uttt_match_create(int32_t device, int32_t max_games, uttt_match_t **out) {
+    if (!out || max_games < 1 || max_games > kMatchMaxGames) {
+        set_error("uttt_match_create: bad arguments (max_games=%d of at most %d)", max_games, kMatchMaxGames);
+        return UTTT_ERR_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device visible");
+        return UTTT_ERR_NODEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
+    if (device < 0 || device >= ndev) {
+        set_error("device %d out of range (%d visible)", device, ndev);
+        return UTTT_ERR_NODEVICE;
+    }
+    HIP_TRY(hipSetDevice(device));
+    uttt_match *m = new uttt_match();
+    m->device = device;
+    m->max_games = max_games;
+    const int64_t n = max_games;
+    int rc = UTTT_OK;
+    if ((rc = m->d_state.grow(n)) || (rc = m->d_roots.grow(2 * n)) || (rc = m->d_ply.grow(n)) ||
+        (rc = m->d_list.grow(2 * n)) || (rc = m->d_action.grow(n * kMaxPlies)) || (rc = m->d_result.grow(n)) ||
+        (rc = m->h_counts.grow(5))) {
+        delete m;
+        return rc;
+    }
+    memset(m->h_counts, 0, 5 * sizeof(int64_t));
+    m->mt.state = m->d_state;
+    m->mt.roots = m->d_roots;
+    m->mt.ply = m->d_ply;
+    m->mt.list = m->d_list;
+    m->mt.action = m->d_action;
+    m->mt.result = m->d_result;
+    m->mt.max_games = max_games;
+    *out = m;
+    return UTTT_OK;
+}
+
+int uttt_match_destroy(uttt_match_t *m) {
+    if (!m) return UTTT_OK;
+    (void)hipSetDevice(m->device);
+    if (m->begun) (void)hipStreamSynchronize(m->stream);
+    delete m;
+    return UTTT_OK;
+}
+
+int uttt_match_begin(uttt_match_t *m, const uttt_state_t *openings, int32_t n_openings, int32_t games, int32_t paired,
+                     int32_t sample_plies, uint64_t seed, void *stream) {
+    if (!m) return UTTT_ERR_ARG;
+    if (int rc = uttt_match_check_host(openings, n_openings, games, m->max_games, paired)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    if (m->begun) HIP_TRY(hipStreamSynchronize(m->stream));  // an earlier match's kernels, before its memory is rewritten
+    m->stream = (hipStream_t)stream;
+    m->begun = false;
+    std::vector<uttt_state_t> start((size_t)games);
+    for (int g = 0; g < games; ++g) start[g] = openings[match_opening_of(g, paired)];
+    HIP_TRY(hipMemcpyAsync(m->mt.state, start.data(), sizeof(uttt_state_t) * games, hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemsetAsync(m->mt.ply, 0, sizeof(int32_t) * games, m->stream));
+    HIP_TRY(hipMemsetAsync(m->mt.action, 0xFF, (size_t)games * kMaxPlies, m->stream));  // -1
+    HIP_TRY(hipMemsetAsync(m->mt.result, 0xFF, (size_t)games, m->stream));              // kMatchLive
+    m->mt.games = games;
+    m->mt.sample_plies = sample_plies;
+    m->mt.seed = seed;
+    if (int rc = launch_match_lists(m)) return rc;
+    HIP_TRY(hipStreamSynchronize(m->stream));  // `start` was read
+    m->begun = true;
+    return UTTT_OK;
+}
+
+int uttt_match_counts(uttt_match_t *m, int64_t out[5]) {
+    if (!m || !out) return UTTT_ERR_ARG;
+    if (!m->begun) {
+        set_error("uttt_match_counts: call uttt_match_begin first");
+        return UTTT_ERR_ORDER;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (!m->moved[0] && !m->moved[1]) {  // (after a move the counters are still the last lists': nothing new to read)
+        for (int i = 0; i < 5; ++i) m->counts[i] = __atomic_load_n(m->h_counts.get() + i, __ATOMIC_ACQUIRE);
+        m->have_counts = true;
+    }
+    for (int i = 0; i < 5; ++i) out[i] = m->counts[i];
+    return UTTT_OK;
+}
+
+int uttt_match_search_begin(uttt_match_t *m, uttt_engine_t *e, int32_t player, int32_t sims, int32_t batch,
+                            int32_t semantics) {
+    if (int rc = match_player_check("uttt_match_search_begin", m, e, player)) return rc;
+    if (int rc = refuse_root_noise(e, "uttt_match_search_begin",
+                                   "a plain search keys it by tree index, which a match changes from ply to ply"))
+        return rc;
+    if (int rc = refuse_tree_reuse(e, "uttt_match_search_begin", "a match's trees change games from ply to ply")) return rc;
+    if (!m->have_counts || m->moved[player]) {
+        set_error("uttt_match_search_begin: player %d's list is stale (call uttt_match_lists, then uttt_match_counts)",
+                  player);
+        return UTTT_ERR_ORDER;
+    }
+    const int64_t n = m->counts[player];
+    if (n <= 0) {
+        set_error("uttt_match_search_begin: player %d is to move in no live game", player);
+        return UTTT_ERR_ARG;
+    }
+    if (n > e->max_trees) {
+        set_error("uttt_match_search_begin: %lld games for an engine of %d trees", (long long)n, e->max_trees);
+        return UTTT_ERR_ARG;
+    }
+    m->searching[player] = nullptr;
+    if (int rc = search_begin_roots(e, "uttt_match_search_begin", m->mt.roots + (size_t)player * m->max_games, (int32_t)n,
+                                    sims, batch, semantics, hipMemcpyDeviceToDevice))
+        return rc;
+    m->searching[player] = e;
+    return UTTT_OK;
+}
+
+int uttt_match_move(uttt_match_t *m, uttt_engine_t *e, int32_t player) {
+    if (int rc = match_player_check("uttt_match_move", m, e, player)) return rc;
+    if (m->moved[player]) {
+        set_error("uttt_match_move: player %d has moved already (call uttt_match_lists)", player);
+        return UTTT_ERR_ORDER;
+    }
+    if (m->searching[player] != e || e->selfplay || e->phase != 1 || e->tr.n_trees != (int32_t)m->counts[player]) {
+        set_error("uttt_match_move: needs the search uttt_match_search_begin began on this engine, every leaf applied");
+        return UTTT_ERR_ORDER;
+    }
+    if (int rc = root_results_ready(e)) return rc;
+    const int n = e->tr.n_trees;
+    hipLaunchKernelGGL(k_root_visits, dim3((n * 81 + 255) / 256), dim3(256), 0, e->stream, e->pool, e->tr,
+                       e->d_visits.get(), e->d_nlegal.get());
+    if (int rc = check_launch()) return rc;
+    hipLaunchKernelGGL(k_match_move, dim3(grid_waves(n)), dim3(kBlock), 0, e->stream, m->mt, (int)player, n,
+                       (const int32_t *)e->d_visits.get(), (const int32_t *)e->d_nlegal.get());
+    m->moved[player] = true;
+    m->searching[player] = nullptr;
+    return check_launch();
+}
+
+int uttt_match_lists(uttt_match_t *m) {
+    if (!m) return UTTT_ERR_ARG;
+    if (!m->begun) {
+        set_error("uttt_match_lists: call uttt_match_begin first");
+        return UTTT_ERR_ORDER;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    return launch_match_lists(m);
+}
+
+int uttt_match_games(uttt_match_t *m, int8_t *results, int32_t *plies, int8_t *actions, uttt_state_t *states) {
+    if (!m) return UTTT_ERR_ARG;
+    if (!m->begun) {
+        set_error("uttt_match_games: call uttt_match_begin first");
+        return UTTT_ERR_ORDER;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t n = (size_t)m->mt.games;
+    if (results) HIP_TRY(hipMemcpyAsync(results, m->mt.result, n, hipMemcpyDeviceToHost, m->stream));
+    if (plies) HIP_TRY(hipMemcpyAsync(plies, m->mt.ply, sizeof(int32_t) * n, hipMemcpyDeviceToHost, m->stream));
+    if (actions) HIP_TRY(hipMemcpyAsync(actions, m->mt.action, n * kMaxPlies, hipMemcpyDeviceToHost, m->stream));
+    if (states) HIP_TRY(hipMemcpyAsync(states, m->mt.state, sizeof(uttt_state_t) * n, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     return UTTT_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include "uttt_bits.h"
 #include "uttt_engine.h"
+#include "uttt_match.h"
 #include "uttt_noise.h"
 #include "uttt_reroot.h"
 #include "uttt_playout.h"
@@ -463,6 +464,71 @@ int uttt_reroot_host(const uint32_t *records, int32_t node_count, const uttt_sta
     }
     *out_count = n;
     return UTTT_OK;
+}
+
+int uttt_match_check_host(const uttt_state_t *openings, int32_t n_openings, int32_t games, int32_t max_games,
+                          int32_t paired) {
+    if (games < 1 || games > max_games) {
+        set_error("uttt_match_begin: %d games outside 1..%d (the match's max_games)", games, max_games);
+        return UTTT_ERR_ARG;
+    }
+    if (paired && (games & 1)) {
+        set_error("uttt_match_begin: a paired match plays every opening twice, and %d games is odd", games);
+        return UTTT_ERR_ARG;
+    }
+    const int need = match_opening_of(games - 1, paired) + 1;
+    if (!openings || n_openings < need) {
+        set_error("uttt_match_begin: %d openings for %d %s games (%d needed)", openings ? n_openings : 0, games,
+                  paired ? "paired" : "unpaired", need);
+        return UTTT_ERR_ARG;
+    }
+    for (int i = 0; i < need; ++i) {
+        if (openings[i].active < -1 || openings[i].active > 8) {
+            set_error("active_board must be -1..8 (opening %d has %d)", i, openings[i].active);
+            return UTTT_ERR_ARG;
+        }
+        if (is_done(openings[i])) {
+            set_error("uttt_match_begin: opening %d is a finished game", i);
+            return UTTT_ERR_ARG;
+        }
+    }
+    return UTTT_OK;
+}
+
+int uttt_match_move_host(const uttt_state_t *state, const int32_t *visits, int32_t n_visits, int32_t ply, int64_t game,
+                         uint64_t seed, int32_t sample_plies, uttt_state_t *next, int32_t *action, int32_t *result) {
+    // uttt_match.h for one game; what k_match_move writes for it.
+    if (!state || !visits || !next || !action || !result || ply < 0 || ply > 80 || game < 0) {
+        set_error("uttt_match_move_host: null pointer, a ply outside 0..80 or a negative game id");
+        return UTTT_ERR_ARG;
+    }
+    if (state->active < -1 || state->active > 8) {
+        set_error("active_board must be -1..8 (the state has %d)", state->active);
+        return UTTT_ERR_ARG;
+    }
+    uint32_t m[3];
+    legal_mask(*state, m);
+    const int L = (int)legal_count(*state);
+    if (L == 0 || n_visits != L) {
+        set_error("uttt_match_move_host: %d visit counts for a state with %d legal moves%s", n_visits, L,
+                  L ? "" : " (a finished game)");
+        return UTTT_ERR_ARG;
+    }
+    for (int i = 0; i < L; ++i)
+        if (visits[i] < 0 || visits[i] > UTTT_MAX_SIMS) {
+            set_error("uttt_match_move_host: visit count %d at rank %d outside 0..%d", visits[i], i, UTTT_MAX_SIMS);
+            return UTTT_ERR_ARG;
+        }
+    const int i = match_choose(visits, L, ply, (uint64_t)game, seed, sample_plies);
+    const int a = nth_legal(m, (uint32_t)i);
+    *next = next_state(*state, a);
+    *action = a;
+    *result = match_result_after(*next, match_player_to_move((int)(game & 1), ply));
+    return UTTT_OK;
+}
+
+uint64_t uttt_match_draw_host(uint64_t seed, int64_t game, int32_t ply) {
+    return match_draw(seed, (uint64_t)game, (uint32_t)ply);
 }
 
 }  // extern "C"

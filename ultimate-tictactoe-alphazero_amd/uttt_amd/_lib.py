@@ -113,6 +113,17 @@ SIGNATURES = {
     "uttt_search_reroot": (ctypes.c_int, [_P, _I32P, _I32]),
     "uttt_search_tree": (ctypes.c_int, [_P, _I32, _U32P, _I32, _I32P]),
     "uttt_reroot_host": (ctypes.c_int, [_U32P, _I32, _SP, _I32, _U32P, _I32P]),
+    "uttt_match_create": (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_P)]),
+    "uttt_match_destroy": (ctypes.c_int, [_P]),
+    "uttt_match_check_host": (ctypes.c_int, [_SP, _I32, _I32, _I32, _I32]),
+    "uttt_match_begin": (ctypes.c_int, [_P, _SP, _I32, _I32, _I32, _I32, _U64, _P]),
+    "uttt_match_counts": (ctypes.c_int, [_P, _I64P]),
+    "uttt_match_search_begin": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32]),
+    "uttt_match_move": (ctypes.c_int, [_P, _P, _I32]),
+    "uttt_match_lists": (ctypes.c_int, [_P]),
+    "uttt_match_games": (ctypes.c_int, [_P, _I8P, _I32P, _I8P, _SP]),
+    "uttt_match_move_host": (ctypes.c_int, [_SP, _I32P, _I32, _I32, _I64, _U64, _I32, _SP, _I32P, _I32P]),
+    "uttt_match_draw_host": (_U64, [_U64, _I64, _I32]),
     "uttt_selfplay_set_temperature_schedule": (ctypes.c_int, [_P, _I32, _F32]),
     "uttt_selfplay_begin": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_uint32, _F32, _I32, _I32, _I64]),
     "uttt_selfplay_move_begin": (ctypes.c_int, [_P, _I32P]),

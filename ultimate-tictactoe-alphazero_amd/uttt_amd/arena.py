@@ -179,6 +179,28 @@ def evaluate_vs_playouts(model, game_count=10, playouts=64, opponent_evaluate_co
     return result
 
 
+def evaluate_network_match(model0, model1, games=1024, opening_plies=4, evaluate_count=50, batch_size=8, sample_plies=0,
+                           seed=0, device=None, make_evaluator=None, symmetry=None, progress=None):
+    """evaluate_network's question asked of a device-resident match (match.play_match): model0 against model1
+    over `games` games from games // 2 random openings of opening_plies plies, each played with both colours,
+    the moves the most visited ones (sample_plies > 0: the first plies sampled from the visit counts). Returns a
+    match.MatchResult: model0's score, the Elo difference and its 95% interval from the pair scores.
+    make_evaluator(model, engine) -> engine evaluator (default: model_evaluator, with `symmetry`)."""
+    from . import match
+    if games < 2 or games % 2:
+        raise ValueError(f"evaluate_network_match: games must be even and at least 2 (got {games})")
+
+    def factory(model):
+        if make_evaluator is not None:
+            return lambda engine: make_evaluator(model, engine)
+        return lambda engine: model_evaluator(model, engine.max_trees, engine, symmetry=symmetry)
+
+    openings = match.random_openings(games // 2, opening_plies, seed)
+    return match.play_match(match.Player(factory(model0), evaluate_count, batch_size),
+                            match.Player(factory(model1), evaluate_count, batch_size), games, openings, paired=True,
+                            sample_plies=sample_plies, seed=seed, device=device, progress=progress)
+
+
 def first_player_value(state):
     """self_play.py:20-25."""
     if state.is_lose():
@@ -227,4 +249,4 @@ def self_play_py(model, game_count, seed_base=0, temperature=1.0, evaluate_count
 
 
 __all__ = ["ModelEvaluator", "first_player_value", "self_play_py", "PvMcts", "evaluate_network", "first_player_point", "model_evaluator",
-           "scores_from_visits", "evaluate_vs_playouts"]
+           "scores_from_visits", "evaluate_vs_playouts", "evaluate_network_match"]

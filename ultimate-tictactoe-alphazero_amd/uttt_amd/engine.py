@@ -499,3 +499,77 @@ class Engine:
         check(self.lib.uttt_engine_kernel_stats(self.h, _lib.KERNELS[name], ctypes.byref(ms), ctypes.byref(ln),
                                                 ctypes.byref(by)))
         return {"ms": ms.value, "launches": ln.value, "bytes": by.value}
+
+
+class Match:
+    """Python handle on a device-resident match (uttt_match_*): the games of two players, each an
+    Engine of its own, both on the stream the match began on. match.play_match drives it."""
+
+    COUNTS = ("to_move_0", "to_move_1", "finished", "half_points_0", "drawn")
+
+    def __init__(self, max_games, device=None):
+        import torch
+
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.EngineError("no ROCm GPU visible to torch; a match runs only on MI355X (gfx950)")
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.max_games = int(max_games)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.uttt_match_create(self.device, self.max_games, ctypes.byref(h)))
+        self.h = h
+        self.games = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.uttt_match_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def begin(self, openings, games, paired=True, sample_plies=0, seed=0, stream=None):
+        """Start `games` games from the host states `openings` on `stream` (default: torch's current stream on
+        the match's device), which both players' engines must use (Engine.use_stream)."""
+        import torch
+
+        op = as_states(openings)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        check(self.lib.uttt_match_begin(self.h, op.ctypes.data_as(ctypes.POINTER(UtttState)), len(op), int(games),
+                                        int(bool(paired)), int(sample_plies),
+                                        ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_void_p(s.cuda_stream)))
+        self.stream = s
+        self.games = int(games)
+
+    def counts(self):
+        """(games where player 0 is to move, games where player 1 is, finished, player 0's half-points, drawn) as
+        of the last lists(); synchronises the stream."""
+        out = np.zeros(5, np.int64)
+        check(self.lib.uttt_match_counts(self.h, ptr(out, ctypes.c_int64)))
+        self._counts = tuple(int(x) for x in out)
+        return self._counts
+
+    def search_begin(self, engine, player, evaluate_count=50, batch_size=8, semantics="py"):
+        """Begin engine's search on player's games (uttt_match_search_begin); select / apply rounds follow."""
+        check(self.lib.uttt_match_search_begin(self.h, engine.h, int(player), int(evaluate_count), int(batch_size),
+                                               Engine.SEMANTICS[semantics]))
+        engine.n_trees = self._counts[int(player)]  # (the C call refused a list no counts() had read)
+
+    def move(self, engine, player):
+        check(self.lib.uttt_match_move(self.h, engine.h, int(player)))
+
+    def lists(self):
+        check(self.lib.uttt_match_lists(self.h))
+
+    def state(self):
+        """{"results": int8 (games,), "plies": int32 (games,), "actions": int8 (games, 81), "states": STATE_DTYPE}."""
+        n = self.games
+        res, ply = np.zeros(n, np.int8), np.zeros(n, np.int32)
+        act, st = np.zeros((n, 81), np.int8), np.zeros(n, STATE_DTYPE)
+        check(self.lib.uttt_match_games(self.h, ptr(res, ctypes.c_int8), ptr(ply, ctypes.c_int32),
+                                        ptr(act, ctypes.c_int8), st.ctypes.data_as(ctypes.POINTER(UtttState))))
+        return {"results": res, "plies": ply, "actions": act, "states": st}
